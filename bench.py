@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- headline measurement of the PCD prover hot path on MI355X.
 
-Metric (BASELINE.json): MSM Mscalar-mul/s on MNT4-298 G1 at n = 2^20 (proving key resident), plus the PCD-step
-prover-arithmetic time, reported in the same JSON line:
+Metric (BASELINE.json): MSM Mscalar-mul/s on MNT4-298 G1 at n = 2^20 (proving key resident).  A plain run measures that alone: set-up,
+W warm-up steps, K timed steps one MSM at a time, and the JSON line (`value`, `ms_per_step`, the plan in `config`).  With --full the same
+line also carries everything below -- pipelined MSMs, stage timings and rooflines, the CPU baseline with its parity check -- and the
+PCD-step prover-arithmetic time:
   pcd_step      main Groth16 proof over MNT4-298 (domain 2^20) + help proof over MNT6-298 (2^16)
   pcd_step_753  BASELINE configs[2] / north_star target: main proof over MNT4-753 (domain 2^20) + help proof over MNT6-753
                 (mixed-radix domain 5 * 2^14), with the roofline of its dominant kernel (G1-753 bucket accumulation)
@@ -20,9 +22,11 @@ all-gather of one Jacobian point per rank + a local EC-add kernel
             the G2 / whole-step multiply-add fractions of the 753-bit step
   --strong  the fixed-total run (2^--log-n pairs, default 2^20) is the headline value (`scaling: strong`)
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+  --dump-outputs DIR  the result of the last timed step, as .npy files (dump_outputs); the inputs are seeded, so two builds compare file for file
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W [--strong]
+        bench.py --gpus N --steps K --warmup W [--strong] [--full]
 """
 import argparse
 import json
@@ -76,7 +80,14 @@ def main():
     ap.add_argument("--no-pipeline", action="store_true", help="headline = one MSM at a time (no second MSM in flight)")
     ap.add_argument("--no-merge", action="store_true", help="N > 1: skip the PCD-step section (merge-node proof over all devices + DAG branches)")
     ap.add_argument("--merge-log-n", type=int, default=20, help="N > 1: log2 of the merge node's domain (20; 22 = BASELINE configs[4], ~10 min of host work)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: pipelined MSMs, stage timings and rooflines, host scalars, CPU baseline, strong scaling, "
+                         "FFT, pairing, KZG and both PCD steps (the --no-* options select among these); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result of the last one to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # stdout carries exactly ONE line, the JSON result: everything else that libraries print there while we run (RCCL's
     # version banner at communicator creation, for one) is sent to stderr by pointing fd 1 at fd 2 until the result is ready
@@ -132,6 +143,7 @@ def single_gpu_fallback(args, reason, world):
                         "PCD_BENCH_FORCE_DIST", "PCD_BENCH_INJECT_FAILURE", "PCD_BENCH_DEVICES") and not k.startswith("TORCHELASTIC")}
     env.setdefault("HIP_VISIBLE_DEVICES", os.environ.get("LOCAL_RANK", "0"))
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-step", "--no-strong"]
+    cmd += ["--full"] if args.full else []
     out = {"metric": "msm_mscalar_mul_per_s", "value": None, "unit": "Mscalar-mul/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "higher_is_better": True}
     try:
@@ -320,6 +332,15 @@ def run(args, stdout_fd):
     for _ in range(10):   # let the clocks settle before the first timed region (the W warm-up steps of each region follow)
         ctx.msm(bases, sbuf)
     elapsed_sync, res = timed_msm(bases, sbuf, args.steps, args.warmup)                 # one MSM at a time: the latency view
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, co, res)
+    c_bits, W, copies = ctx.bases_info(bases)
+    if not args.full:
+        if rank == 0:
+            emit(headline(args, world, n_local, elapsed_sync, headline_strong, c_bits, W, copies, upload_s), stdout_fd)
+        if use_dist:
+            dist.destroy_process_group()
+        return 0
     elapsed, res = timed_msm(bases, sbuf, args.steps, args.warmup, depth) if depth > 1 else (elapsed_sync, res)
     stages = stage_times(bases, sbuf)
     # the same MSM with the scalars coming from the HOST on every call (pcdhip_msm: 42 MB over PCIe inside the call) -- what a caller pays whose
@@ -337,7 +358,6 @@ def run(args, stdout_fd):
                 raise SystemExit("pcdhip_msm (host scalars) and pcdhip_msm_dev (resident scalars) disagree")
             host_scalars[kind] = float(np.median(ts))
     mad_peak_live = ctx.mad_rate()   # the v_mad_u64_u32 issue rate of THIS box, right behind the kernels it prices (boxes differ by ~10 % in sustained clock)
-    c_bits, W, copies = ctx.bases_info(bases)
 
     # ---- correctness of what was timed (outside the timed region): rank-local partial vs the CPU oracle
     cpu = None
@@ -404,27 +424,15 @@ def run(args, stdout_fd):
                                 variants=not args.no_variants)
 
     if rank == 0:
-        # the headline is SURVEY.md 8d's definition: n / t of ONE MSM at a time (what cpu_baseline times as well); the same K steps with
-        # `msms_in_flight` of them submitted at a time are reported under `pipelining`
         ms_per_step = elapsed_sync / args.steps * 1e3
-        value = world * n_local * args.steps / elapsed_sync / 1e6
         acc = stages["accumulate"]
         mm, mpm, bpp = CONTRACT[CURVE]
         ach_gbs = n_local * bpp / (acc * 1e-3) / 1e9
         traffic, traffic_note = traffic_from_profile()
         executed = n_local * W * madd_mads(CURVE)
         contract = n_local * mm * mpm
-        out = {
-            "metric": "msm_mscalar_mul_per_s", "value": round(value, 3), "unit": "Mscalar-mul/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "strong" if headline_strong else "weak", "vs_baseline": None,
-            "dtype": "u32 (11 x 28-bit unsaturated Montgomery limbs, v_mad_u64_u32 with 64-bit column accumulators)",
-            "data": "synthetic",
-            "config": {"workload": (f"MNT4-298 G1 variable-base MSM, n={n_local} pairs per GPU ({'fixed total 2^%d split over the ranks' % args.log_n if headline_strong else '2^20 per GPU'}), "
-                                    f"proving-key bases and scalars resident in HBM, scalar distribution {'uniform' if args.dist == 0 else 'witness-like'}"),
-                       "curve": "MNT4-298", "group": "G1", "log_n": args.log_n if headline_strong else LOG_N, "sharding": f"point-range x{world}",
-                       "precompute": f"{copies} window-shifted copies of the bases (one per scalar window; one-time, at key upload)",
-                       "window_bits": c_bits, "windows": W, "upload_precompute_s": round(upload_s, 3)},
+        out = headline(args, world, n_local, elapsed_sync, headline_strong, c_bits, W, copies, upload_s)
+        out.update({
             # the BINDING roof of the dominant kernel (integer VALU issue, not HBM and not MFMA); the HBM view is nested under "hbm"
             "roofline": {"bound": "valu_int32_mad", "achieved": round(executed / (acc * 1e-3) / 1e12, 3),
                              "peak": round(MAD_PEAK / 1e12, 2), "unit": "T mad/s", "frac": round(executed / (acc * 1e-3) / MAD_PEAK, 4),
@@ -461,7 +469,7 @@ def run(args, stdout_fd):
             "whole_step_upstream_work_rate": round(contract / (ms_per_step * 1e-3) / MAD_PEAK, 4),   # VERDICT r01's "whole step" figure: contract mads over the WHOLE step's time
             "whole_step_int_frac": round(executed / (ms_per_step * 1e-3) / MAD_PEAK, 4),   # per GPU: executed mads of the accumulate stage over the WHOLE step's time
             "cpu_baseline": cpu,
-        }
+        })
         if strong:
             out["strong"] = strong
         if fft_info:
@@ -478,13 +486,49 @@ def run(args, stdout_fd):
             out["pcd_step_multi_device"] = multi_info
         if pre_info:
             out["preflight"] = pre_info
-        sys.stdout.flush()
-        os.dup2(stdout_fd, 1)
-        print(json.dumps(out), flush=True)
-        os.dup2(2, 1)
+        emit(out, stdout_fd)
     if use_dist:
         dist.destroy_process_group()
     return exit_code
+
+
+def headline(args, world, n_local, elapsed_sync, headline_strong, c_bits, W, copies, upload_s):
+    """the keys every result line carries.  The headline is SURVEY.md 8d's definition: n / t of ONE MSM at a time (what cpu_baseline
+    times as well); with --full, the same K steps with `msms_in_flight` of them submitted at a time are reported under `pipelining`"""
+    return {
+        "metric": "msm_mscalar_mul_per_s", "value": round(world * n_local * args.steps / elapsed_sync / 1e6, 3), "unit": "Mscalar-mul/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed_sync / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "strong" if headline_strong else "weak", "vs_baseline": None,
+        "dtype": "u32 (11 x 28-bit unsaturated Montgomery limbs, v_mad_u64_u32 with 64-bit column accumulators)",
+        "data": "synthetic",
+        "config": {"workload": (f"MNT4-298 G1 variable-base MSM, n={n_local} pairs per GPU ({'fixed total 2^%d split over the ranks' % args.log_n if headline_strong else '2^20 per GPU'}), "
+                                f"proving-key bases and scalars resident in HBM, scalar distribution {'uniform' if args.dist == 0 else 'witness-like'}"),
+                   "curve": "MNT4-298", "group": "G1", "log_n": args.log_n if headline_strong else LOG_N, "sharding": f"point-range x{world}",
+                   "precompute": f"{copies} window-shifted copies of the bases (one per scalar window; one-time, at key upload)",
+                   "window_bits": c_bits, "windows": W, "upload_precompute_s": round(upload_s, 3)},
+    }
+
+
+def emit(out, stdout_fd):
+    """the one line on the real stdout (fd 1 points at stderr everywhere else: see main)"""
+    sys.stdout.flush()
+    os.dup2(stdout_fd, 1)
+    print(json.dumps(out), flush=True)
+    os.dup2(2, 1)
+
+
+def dump_outputs(path, co, res):
+    """--dump-outputs: what the last timed step returned, for comparing two builds output for output.  A step returns one Jacobian
+    point, and a point has many Jacobian representatives (two correct builds may differ in Z), so what is written is its affine image:
+      msm_result_xy.npy    float32 [2, 40]  x and y in canonical form, the little-endian bytes of each coordinate (exact in float32)
+      msm_result_inf.npy   float32 [1]      1 if the result is the point at infinity (x and y are then 0)
+    The inputs are seeded: the same arguments give the same inputs and, from a correct build, the same files."""
+    os.makedirs(path, exist_ok=True)
+    xy, inf = co.to_affine(CURVE, GROUP, res)
+    words = co.FIELD_N64[co.CURVE_FQ[CURVE]]
+    canon = co.fp_op(co.CURVE_FQ[CURVE], "to_canonical", np.ascontiguousarray(xy.reshape(2, words)))
+    np.save(os.path.join(path, "msm_result_xy.npy"), canon.astype("<u8").view(np.uint8).reshape(2, 8 * words).astype(np.float32))
+    np.save(os.path.join(path, "msm_result_inf.npy"), inf.astype(np.float32))
 
 
 def source_sha16():
