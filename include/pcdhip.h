@@ -422,6 +422,36 @@ int pcdhip_vk_serialize(int curve_id, const uint64_t* alpha_g1, const uint64_t* 
 int pcdhip_vk_deserialize(int curve_id, const uint8_t* in, size_t in_len, int compressed, uint64_t* alpha_g1, uint64_t* beta_g2, uint64_t* gamma_g2,
                           uint64_t* delta_g2, uint64_t* gamma_abc_g1, uint8_t* gamma_abc_inf, size_t max_inputs, size_t* num_inputs);
 
+/* ---- K7 open side: KZG10 / MarlinKZG10 openings ------------------------------------------------------------------------
+ * The open half of ark-poly-commit's KZG10 (the commit half is the prefix MSM above over the resident powers).  Polynomials are
+ * device vectors of ABI Montgomery coefficients, low degree first (lens[j] of them, at most the buffer's n); field elements are in
+ * ABI Montgomery form, MSM scalars stay canonical.  Every division / evaluation runs on the device in three stream-ordered launches
+ * (tile values, one carry scan, the tiles again from their carries); only the pairing check's scalar bookkeeping is on the host. */
+/* ark-poly `evaluate`: out_mont[j] = polys[j](z), the k polynomials in one launch per phase (all of one field; len 0 gives 0) */
+int pcdhip_poly_eval(pcdhip_ctx* ctx, const pcdhip_buf* const* polys, const size_t* lens, size_t k, const uint64_t* z_mont,
+                     uint64_t* out_mont);
+/* MarlinKZG10's combined polynomial: out_i = sum_j coeffs_j p_(j,i) for i < *out_len = max lens (out may be one of the inputs) */
+int pcdhip_poly_lincomb(pcdhip_ctx* ctx, const pcdhip_buf* const* polys, const size_t* lens, const uint64_t* coeffs_mont, size_t k,
+                        pcdhip_buf* out, size_t* out_len);
+/* ark-poly `&p / &DensePolynomial([-z, 1])`: len-1 quotient coefficients (none for len <= 1), remainder = p(z).  q may be null when
+ * len <= 1 and must not be p's buffer. */
+int pcdhip_poly_div_linear(pcdhip_ctx* ctx, const pcdhip_buf* p, size_t len, const uint64_t* z_mont, pcdhip_buf* q,
+                           uint64_t* value_mont);
+/* ark-poly-commit KZG10::open (+ p(z)): w = MSM(powers_of_g, p/(X-z)) + MSM(powers_of_gamma_g, blinding/(X-z)),
+   random_v = blinding(z); blinding == NULL: no hiding part, random_v untouched.  w is Jacobian (X || Y || Z).  PCDHIP_E_ARG when
+   a quotient has more coefficients than its bases (upstream's TooManyCoefficients), for a field that is not the curve's scalar
+   field, and for sharded bases.  It runs on the context's own stream and workspaces, which MSM tickets do not use. */
+int pcdhip_kzg_open(pcdhip_ctx* ctx, const pcdhip_bases* powers_of_g, const pcdhip_bases* powers_of_gamma_g, const pcdhip_buf* p,
+                    size_t len, const pcdhip_buf* blinding, size_t blinding_len, const uint64_t* z_mont, uint64_t* w_xyz_mont,
+                    uint64_t* value_mont, uint64_t* random_v_mont);
+/* KZG10::check (n == 1, randomizers may be NULL) and KZG10::batch_check (caller's randomizers, canonical, the first
+   1 as upstream): ok = [ e(sum r_i (C_i + z_i W_i) - (sum r_i v_i) g - (sum r_i rv_i) gamma_g, h) == e(sum r_i W_i, beta_h) ].
+   Affine G1 / G2 points (x || y, flags nullable); n == 0 is true. */
+int pcdhip_kzg_check(pcdhip_ctx* ctx, int curve_id, const uint64_t* g_xy, const uint64_t* gamma_g_xy, const uint64_t* h_xy,
+                     const uint64_t* beta_h_xy, size_t n, const uint64_t* comms_xy, const uint8_t* comms_inf, const uint64_t* points_mont,
+                     const uint64_t* values_mont, const uint64_t* w_xy, const uint8_t* w_inf, const uint64_t* random_v_mont,
+                     const uint64_t* randomizers_canonical, int* ok);
+
 /* ---- timing helpers (HIP events on the context's stream, for bench.py) ------------------------- */
 int pcdhip_timer_start(pcdhip_ctx* ctx);
 int pcdhip_timer_stop(pcdhip_ctx* ctx, float* out_ms);

@@ -61,6 +61,7 @@ EXPORTS = [
     "pcdhip_proof_deserialize", "pcdhip_vk_serialized_size", "pcdhip_vk_serialize", "pcdhip_vk_deserialize",
     "pcdhip_process_vk", "pcdhip_pvk_free", "pcdhip_groth16_verify_prepared", "pcdhip_groth16_verify_batch_rlc",
     "pcdhip_multi_pairing", "pcdhip_pairing_set_mode", "pcdhip_groth16_verify", "pcdhip_groth16_verify_batch", "pcdhip_timer_start", "pcdhip_timer_stop",
+    "pcdhip_poly_eval", "pcdhip_poly_lincomb", "pcdhip_poly_div_linear", "pcdhip_kzg_open", "pcdhip_kzg_check",
 ]
 
 
@@ -518,6 +519,72 @@ class Context:
         rho = _u64(rho).reshape(k, 2)
         ok = C.c_int(0)
         self._check(lib().pcdhip_groth16_verify_batch_rlc(self._ctx, pvk._h, C.c_size_t(k), _p(pi), _p(pr), _p(pinf), _p(rho), C.byref(ok)))
+        return ok.value == 1
+
+    # ---- K7: the open side of KZG10 / MarlinKZG10
+    @staticmethod
+    def _polys(polys, lens):
+        lens = [p.n for p in polys] if lens is None else [int(x) for x in lens]
+        k = len(polys)
+        arr = (C.c_void_p * max(k, 1))(*[p._h.value for p in polys])
+        ln = (C.c_size_t * max(k, 1))(*lens)
+        return arr, ln, k
+
+    def poly_eval(self, polys, z_mont, lens=None):
+        """ark-poly `evaluate` of k polynomials (DeviceBufs of one field, lens[j] coefficients) at z -> (k, L) ABI Montgomery values"""
+        arr, ln, k = self._polys(polys, lens)
+        out = np.zeros((k, FIELD_LIMBS[polys[0].field] if k else 1), dtype=np.uint64)
+        self._check(lib().pcdhip_poly_eval(self._ctx, arr, ln, C.c_size_t(k), _p(_u64(z_mont)), _p(out)))
+        return out
+
+    def poly_lincomb(self, polys, coeffs_mont, out, lens=None):
+        """out_i = sum_j coeffs_j p_(j,i) into the DeviceBuf `out` -> the length written (the longest input)"""
+        arr, ln, k = self._polys(polys, lens)
+        cf = _u64(coeffs_mont) if k else np.zeros(1, dtype=np.uint64)
+        n = C.c_size_t(0)
+        self._check(lib().pcdhip_poly_lincomb(self._ctx, arr, ln, _p(cf), C.c_size_t(k), out._h, C.byref(n)))
+        return n.value
+
+    def poly_div_linear(self, p, z_mont, length=None, q=None):
+        """p / (X - z) -> (quotient DeviceBuf of length - 1 coefficients, or None for length <= 1; p(z))"""
+        length = p.n if length is None else int(length)
+        own = q is None and length > 1
+        if own:
+            h = C.c_void_p()
+            self._check(lib().pcdhip_buf_alloc(self._ctx, p.field, C.c_size_t(length - 1), C.byref(h)))
+            q = DeviceBuf(self, h, p.field, length - 1)
+        v = np.zeros(FIELD_LIMBS[p.field], dtype=np.uint64)
+        rc = lib().pcdhip_poly_div_linear(self._ctx, p._h, C.c_size_t(length), _p(_u64(z_mont)), q._h if q is not None else None, _p(v))
+        if rc and own:
+            q.free()
+        self._check(rc)
+        return q, v
+
+    def kzg_open(self, powers_of_g, p, z_mont, length=None, powers_of_gamma_g=None, blinding=None, blinding_len=None):
+        """KZG10::open -> (w Jacobian X||Y||Z, p(z), blinding(z) or None when there is no blinding polynomial)"""
+        length = p.n if length is None else int(length)
+        bl = 0 if blinding is None else (blinding.n if blinding_len is None else int(blinding_len))
+        w = np.zeros(3 * point_limbs(powers_of_g.curve, powers_of_g.group) // 2, dtype=np.uint64)
+        v = np.zeros(FIELD_LIMBS[p.field], dtype=np.uint64)
+        rv = np.zeros_like(v)
+        self._check(lib().pcdhip_kzg_open(self._ctx, powers_of_g._h, powers_of_gamma_g._h if powers_of_gamma_g is not None else None, p._h,
+                                          C.c_size_t(length), blinding._h if blinding is not None else None, C.c_size_t(bl),
+                                          _p(_u64(z_mont)), _p(w), _p(v), _p(rv)))
+        return w, v, (rv if blinding is not None else None)
+
+    def kzg_check(self, curve, g_xy, h_xy, beta_h_xy, comms_xy, points_mont, values_mont, w_xy, gamma_g_xy=None, random_v_mont=None,
+                  randomizers_canonical=None, comms_inf=None, w_inf=None):
+        """KZG10::check (one opening) / batch_check (n openings, randomizers canonical, the first 1) -> bool"""
+        l1, fl = point_limbs(curve, G1), FIELD_LIMBS[CURVE_FR[curve]]
+        cm = _u64(comms_xy).reshape(-1, l1)
+        n = cm.shape[0]
+        arr = lambda a, w: None if a is None else _u64(a).reshape(n, w)
+        flags = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint8)
+        ok = C.c_int(0)
+        self._check(lib().pcdhip_kzg_check(self._ctx, curve, _p(_u64(g_xy)), _p(None if gamma_g_xy is None else _u64(gamma_g_xy)),
+                                           _p(_u64(h_xy)), _p(_u64(beta_h_xy)), C.c_size_t(n), _p(cm), _p(flags(comms_inf)),
+                                           _p(arr(points_mont, fl)), _p(arr(values_mont, fl)), _p(arr(w_xy, l1)), _p(flags(w_inf)),
+                                           _p(arr(random_v_mont, fl)), _p(arr(randomizers_canonical, fl)), C.byref(ok)))
         return ok.value == 1
 
     # ---- timing

@@ -183,6 +183,8 @@ struct GroupEntry {
 const GroupEntry& group_entry(int curve_id, int group_id);  // group_id 1 / 2
 
 // ---- per-field entries (inst_field.hip) ------------------------------------------------------------
+// one polynomial of the K7 kernels (poly.hip.h): `len` coefficients in the C-ABI Montgomery image, low degree first
+struct PolyDesc { const uint32_t* p; uint64_t len; };
 struct FieldEntry {
   int words;      // u32 words per element, device-internal image
   int abi_words;  // u32 words per element at the C-ABI
@@ -221,6 +223,14 @@ struct FieldEntry {
                                 uint32_t batch);
   // the three mat-vecs of a witness map in one launch (two with long rows): out, out + stride, out + 2 stride; matrix 0 appends the inputs
   hipError_t (*spmv3)(hipStream_t, const DevCsr mats[3], const uint32_t* z, uint32_t num_inputs, uint32_t n, uint32_t* out, size_t stride_words);
+  // K7 open side (poly.hip.h).  poly_eval: the k polynomials of descs_dev (on the device) at z (C-ABI words, host) -> values_abi_dev
+  // (k elements); scratch: poly_scratch_words(k, max_len) u32 words.  With div (host copy of the single descriptor, k == 1) also the
+  // quotient by (X - z), div->len - 1 elements into q_out: C-ABI Montgomery, or canonical words when q_canonical
+  size_t (*poly_scratch_words)(uint32_t k, uint64_t max_len);
+  hipError_t (*poly_eval)(hipStream_t, const PolyDesc* descs_dev, uint32_t k, uint64_t max_len, const uint32_t* z_abi, uint32_t* scratch,
+                          uint32_t* values_abi_dev, const PolyDesc* div, uint32_t* q_out, int q_canonical);
+  // out_i = sum_j c_j p_(j,i) for i < n_out (C-ABI Montgomery everywhere; coeffs_abi_dev on the device; out may alias an input)
+  hipError_t (*poly_lincomb)(hipStream_t, const PolyDesc* descs_dev, const uint32_t* coeffs_abi_dev, uint32_t k, uint64_t n_out, uint32_t* out);
 };
 const FieldEntry& field_entry(int field_id);
 

@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include "fft.hip.h"
+#include "poly.hip.h"
 
 namespace pcd {
 
@@ -462,13 +463,45 @@ hipError_t setup_scalars(hipStream_t st, const void* domain_consts, const uint32
   return hipGetLastError();
 }
 
+// ---- K7 open side (poly.hip.h): division by (X - z), evaluation, linear combination.  The products inlined, as in the transform
+// passes (FTP): the operands of a call would travel through scratch.
+typedef PolyCfg<FTP> PC;
+uint64_t poly_tiles(uint64_t len) { return std::max<uint64_t>(1, (len + PC::TILE - 1) / PC::TILE); }
+size_t poly_scratch_words(uint32_t k, uint64_t max_len) { return (2 * (size_t)k * poly_tiles(max_len) + 1) * EW; }  // tiles, carries, z^TILE
+hipError_t poly_eval(hipStream_t st, const PolyDesc* descs_dev, uint32_t k, uint64_t max_len, const uint32_t* z_abi, uint32_t* scratch,
+                     uint32_t* values_abi_dev, const PolyDesc* div, uint32_t* q_out, int q_canonical) {
+  if (k == 0) return hipSuccess;
+  if (k > 65535 || (div && k != 1)) return hipErrorInvalidValue;
+  PolyAbiElt<FTP> z;
+  memcpy(z.w, z_abi, sizeof z.w);
+  const uint64_t K = poly_tiles(max_len);
+  uint32_t* tiles = scratch;
+  uint32_t* carries = scratch + (size_t)k * K * EW;
+  uint32_t* zt = carries + (size_t)k * K * EW;
+  hipLaunchKernelGGL(poly_tile_eval<FTP>, dim3((uint32_t)K, k), dim3(PC::B), 0, st, descs_dev, z, tiles, (uint32_t)K, zt);
+  hipLaunchKernelGGL(poly_carry_scan<FTP>, dim3(1, k), dim3(PC::CB), 0, st, descs_dev, tiles, (uint32_t)K, zt, div ? carries : nullptr,
+                     values_abi_dev);
+  if (div && div->len > 1) {
+    const dim3 gd((uint32_t)poly_tiles(div->len)), bd(PC::B);
+    if (q_canonical) hipLaunchKernelGGL((poly_div_tile<FTP, true>), gd, bd, 0, st, div->p, div->len, z, carries, q_out);
+    else hipLaunchKernelGGL((poly_div_tile<FTP, false>), gd, bd, 0, st, div->p, div->len, z, carries, q_out);
+  }
+  return hipGetLastError();
+}
+hipError_t poly_lincomb_run(hipStream_t st, const PolyDesc* descs_dev, const uint32_t* coeffs_abi_dev, uint32_t k, uint64_t n_out, uint32_t* out) {
+  if (n_out == 0) return hipSuccess;
+  hipLaunchKernelGGL(poly_lincomb<FTP>, dim3((uint32_t)((n_out + 255) / 256)), dim3(256), 0, st, descs_dev, coeffs_abi_dev, k, n_out, out);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 #define PCD_CAT_(a, b) a##b
 #define PCD_CAT(a, b) PCD_CAT_(a, b)
 const FieldEntry* PCD_CAT(pcd_field_entry_, PCD_FIELD_IDX)() {
   static const FieldEntry e = {EW, FT::ABI_WORDS, FT::Params::TWO_ADICITY, make_tables, run, convert, spmv, small_abi, mul_sub_divz,
-                               mixed_make_tables, mixed_run, mixed_mul_sub_divz, scale_canon, SETUP_CONSTS, setup_scalars, run_batched_entry, spmv3};
+                               mixed_make_tables, mixed_run, mixed_mul_sub_divz, scale_canon, SETUP_CONSTS, setup_scalars, run_batched_entry, spmv3,
+                               poly_scratch_words, poly_eval, poly_lincomb_run};
   return &e;
 }
 

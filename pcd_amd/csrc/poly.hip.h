@@ -1,0 +1,209 @@
+// K7, the open side of KZG10 / MarlinKZG10 (ark-poly-commit `KZG10::open`, `MarlinKZG10::open`): division of a polynomial by
+// (X - z), evaluation of k polynomials at one point, and the linear combination of k polynomials, on gfx950.
+//
+// Coefficients are C-ABI Montgomery words (x R, R = 2^(32 ABI_WORDS)), low degree first, as in a pcdhip_buf.  The kernels never
+// convert them: unpack32 reads x R as a plain integer, and since every step below is LINEAR in the coefficients (only the point z,
+// brought into the device image once per lane, enters a product), the results come out scaled by the same R -- pack32 of the
+// canonical representative IS the ABI image of the result.  A coefficient costs its Horner product and nothing else; the canonical
+// words the MSM wants (x itself) cost one product more, fused into the store.
+//
+// Division.  p(X) = q(X)(X - z) + v with h_i = sum_{j >= i} p_j z^(j - i): h_i = p_i + z h_(i+1), q_(i-1) = h_i, v = h_0.
+// A suffix scan with a constant multiplier, in three stream-ordered launches (no inter-workgroup waiting):
+//   1. poly_tile_eval   -- every tile of TILE = B x E coefficients reduces to T_k = sum_j p_(lo_k + j) z^j;
+//   2. poly_carry_scan  -- one workgroup scans the T_k with the multiplier z^TILE: the carry-in C_k = h at the tile's end, and v;
+//   3. poly_div_tile    -- every tile again, from its carry-in: q.
+// Inside a tile a lane owns E consecutive coefficients (a local Horner), the B lanes combine (value, multiplier) pairs over log2(B)
+// steps whose multiplier is the same power of z in every lane (it squares once per step).  Tiles are staged through LDS, so the
+// global reads (and the shifted-by-one quotient stores) are contiguous word streams.
+#pragma once
+#include "ec.hip.h"
+
+namespace pcd {
+
+template <class F>
+struct PolyAbiElt { uint32_t w[F::ABI_WORDS]; };
+
+// B lanes, E coefficients per lane (PolyCfg<F>::B, ::E): 298-bit tiles of 1024 (LDS 40 + 11 KB), 753-bit tiles of 512 (48 + 14 KB)
+template <class F>
+struct PolyCfg {
+  static constexpr int B = F::N <= 11 ? 256 : 128;
+  static constexpr int E = 4;
+  static constexpr uint32_t TILE = (uint32_t)B * E;
+  static constexpr int CB = 256;  // lanes of the carry scan
+};
+
+// stage `cnt` elements (ABI words) starting at element `lo` of p into LDS, zeros up to the tile's end
+template <class F, int B>
+PCD_DEV void poly_stage_in(const uint32_t* __restrict__ p, uint64_t lo, uint32_t cnt, uint32_t tile, uint32_t* st) {
+  constexpr int AW = F::ABI_WORDS;
+  const uint32_t words = cnt * AW;
+  const uint32_t* src = p + lo * AW;
+  for (uint32_t w = threadIdx.x; w < tile * AW; w += B) st[w] = w < words ? src[w] : 0u;
+}
+
+// tree reduction over the B lanes of (h, segment multiplier m): lane 0 ends with sum_t h_t m^t; m ends as m^B
+template <class F, int B>
+PCD_DEV F poly_block_reduce(F h, F& m, uint32_t* red) {
+  const uint32_t t = threadIdx.x;
+  for (int d = 1; d < B; d <<= 1) {
+    if ((t & (2 * d - 1)) == (uint32_t)d) h.store(red + (size_t)t * F::WORDS);
+    __syncthreads();
+    if ((t & (2 * d - 1)) == 0) h = h + m * F::load(red + (size_t)(t + d) * F::WORDS);
+    __syncthreads();
+    m = m.sqr();
+  }
+  return h;
+}
+
+// inclusive suffix scan: lane t ends with sum_{u >= t} h_u m^(u - t)
+template <class F, int B>
+PCD_DEV F poly_block_suffix_scan(F h, F m, uint32_t* red) {
+  const uint32_t t = threadIdx.x;
+  for (int d = 1; d < B; d <<= 1) {
+    h.store(red + (size_t)t * F::WORDS);
+    __syncthreads();
+    if (t + d < (uint32_t)B) h = h + m * F::load(red + (size_t)(t + d) * F::WORDS);
+    __syncthreads();
+    if (2 * d < B) m = m.sqr();
+  }
+  return h;
+}
+
+// local Horner over a lane's E staged coefficients: h <- sum_e p_e z^e + z^E h
+template <class F, int E>
+PCD_DEV F poly_lane_horner(const uint32_t* st, F h, bool h_zero, const F& z) {
+  constexpr int AW = F::ABI_WORDS;
+  const uint32_t base = threadIdx.x * E;
+#pragma unroll 1
+  for (int e = E - 1; e >= 0; e--) {
+    const F x = F::unpack32(st + (size_t)(base + e) * AW);
+    h = (h_zero && e == E - 1) ? x : x + z * h;
+  }
+  return h;
+}
+
+// phase 1, batched over the polynomials of `descs` (blockIdx.y): tiles[y * tiles_stride + k] = T_k (device image).  Block (0, 0)
+// also leaves z^TILE in zt for the carry scan.
+template <class F>
+__global__ void __launch_bounds__(PolyCfg<F>::B) poly_tile_eval(const PolyDesc* __restrict__ descs, const PolyAbiElt<F> z_abi,
+                                                                uint32_t* __restrict__ tiles, uint32_t tiles_stride, uint32_t* __restrict__ zt) {
+  constexpr int B = PolyCfg<F>::B, E = PolyCfg<F>::E;
+  constexpr uint32_t TILE = PolyCfg<F>::TILE;
+  __shared__ __attribute__((aligned(16))) uint32_t st[TILE * F::ABI_WORDS];
+  __shared__ __attribute__((aligned(16))) uint32_t red[B * F::WORDS];
+  const PolyDesc d = descs[blockIdx.y];
+  const uint64_t lo = (uint64_t)blockIdx.x * TILE;
+  if (blockIdx.x > 0 && lo >= d.len) return;  // (whole workgroup; tile 0 of an empty polynomial runs and yields 0)
+  const uint32_t cnt = lo >= d.len ? 0u : (uint32_t)(d.len - lo < TILE ? d.len - lo : TILE);
+  poly_stage_in<F, B>(d.p, lo, cnt, TILE, st);
+  const F z = F::from_abi(z_abi.w);
+  F m = z;
+#pragma unroll
+  for (int e = 1; e < E; e++) m = m * z;  // z^E
+  __syncthreads();
+  F h = poly_lane_horner<F, E>(st, F::zero(), true, z);
+  h = poly_block_reduce<F, B>(h, m, red);
+  if (threadIdx.x == 0) {
+    h.store(tiles + ((size_t)blockIdx.y * tiles_stride + blockIdx.x) * F::WORDS);
+    if (blockIdx.x == 0 && blockIdx.y == 0) m.store(zt);  // m = (z^E)^B
+  }
+}
+
+// phase 2, one workgroup per polynomial: lane t owns the tiles [t c, t c + c) (c = ceil(K / CB)), a Horner in Z = z^TILE from the
+// top, a suffix scan of the lanes with Z^c, then the walk down that writes the carry-in of every tile (carries may be null) and,
+// from lane 0, v = h_0 as an ABI Montgomery element.
+template <class F>
+__global__ void __launch_bounds__(PolyCfg<F>::CB) poly_carry_scan(const PolyDesc* __restrict__ descs, const uint32_t* __restrict__ tiles,
+                                                                  uint32_t tiles_stride, const uint32_t* __restrict__ zt,
+                                                                  uint32_t* __restrict__ carries, uint32_t* __restrict__ values_abi) {
+  constexpr int CB = PolyCfg<F>::CB;
+  constexpr uint32_t TILE = PolyCfg<F>::TILE;
+  __shared__ __attribute__((aligned(16))) uint32_t red[CB * F::WORDS];
+  const PolyDesc d = descs[blockIdx.y];
+  const uint32_t K = (uint32_t)((d.len + TILE - 1) / TILE);
+  const uint32_t c = (K + CB - 1) / CB;
+  const uint32_t lo = min(K, threadIdx.x * c), hi = min(K, lo + c);
+  const uint32_t* T = tiles + (size_t)blockIdx.y * tiles_stride * F::WORDS;
+  const F Z = K > 1 ? F::load(zt) : F::one();
+  F h = F::zero();
+  for (uint32_t k = hi; k-- > lo;) h = F::load(T + (size_t)k * F::WORDS) + Z * h;
+  h = poly_block_suffix_scan<F, CB>(h, Z.pow_u64(c), red);
+  h.store(red + (size_t)threadIdx.x * F::WORDS);  // (the scan ends on a barrier behind its last reads of red)
+  __syncthreads();
+  F cin = threadIdx.x + 1 < (uint32_t)CB ? F::load(red + (size_t)(threadIdx.x + 1) * F::WORDS) : F::zero();
+  for (uint32_t k = hi; k-- > lo;) {
+    if (carries) cin.store(carries + ((size_t)blockIdx.y * tiles_stride + k) * F::WORDS);
+    cin = F::load(T + (size_t)k * F::WORDS) + Z * cin;
+  }
+  if (threadIdx.x == 0) cin.canonical().pack32(values_abi + (size_t)blockIdx.y * F::ABI_WORDS);
+}
+
+// phase 3 (one polynomial): every tile from its carry-in; q_(i-1) = h_i for the tile's i >= 1, as ABI Montgomery words or, with
+// CANON, as canonical words (x = (x R) (R' / R) / R': one product with the constant cin * 1).
+template <class F, bool CANON>
+__global__ void __launch_bounds__(PolyCfg<F>::B) poly_div_tile(const uint32_t* __restrict__ p, uint64_t len, const PolyAbiElt<F> z_abi,
+                                                               const uint32_t* __restrict__ carries, uint32_t* __restrict__ q) {
+  constexpr int B = PolyCfg<F>::B, E = PolyCfg<F>::E, AW = F::ABI_WORDS;
+  constexpr uint32_t TILE = PolyCfg<F>::TILE;
+  __shared__ __attribute__((aligned(16))) uint32_t st[TILE * AW];
+  __shared__ __attribute__((aligned(16))) uint32_t red[B * F::WORDS];
+  const uint64_t lo = (uint64_t)blockIdx.x * TILE;
+  const uint32_t cnt = (uint32_t)(len - lo < TILE ? len - lo : TILE);
+  poly_stage_in<F, B>(p, lo, cnt, TILE, st);
+  const F z = F::from_abi(z_abi.w);
+  F m = z;
+#pragma unroll
+  for (int e = 1; e < E; e++) m = m * z;
+  const F C = F::load(carries + (size_t)blockIdx.x * F::WORDS);
+  const bool top = threadIdx.x == B - 1;
+  __syncthreads();
+  F h = poly_lane_horner<F, E>(st, top ? C : F::zero(), !top, z);
+  h = poly_block_suffix_scan<F, B>(h, m, red);
+  h.store(red + (size_t)threadIdx.x * F::WORDS);  // (every lane is past the scan's last barrier, which ended all reads of red)
+  __syncthreads();
+  F hin = top ? C : F::load(red + (size_t)(threadIdx.x + 1) * F::WORDS);
+  F kc = F::zero();
+  if constexpr (CANON) {
+    F cin, one_raw = F::zero();
+#pragma unroll
+    for (int i = 0; i < F::N; i++) cin.v[i] = F::Params::cin(i);
+    one_raw.v[0] = 1;
+    kc = cin * one_raw;
+  }
+  const uint32_t base = threadIdx.x * E;
+#pragma unroll 1
+  for (int e = E - 1; e >= 0; e--) {
+    uint32_t* s = st + (size_t)(base + e) * AW;
+    hin = F::unpack32(s) + z * hin;
+    if constexpr (CANON) (hin * kc).canonical().pack32(s);
+    else hin.canonical().pack32(s);
+  }
+  __syncthreads();
+  // element lo + i lands at q[lo + i - 1]: one contiguous run of words from q + (lo - 1) AW (element 0 of the polynomial is v)
+  const uint32_t skip = lo == 0 ? AW : 0;
+  for (uint32_t w = threadIdx.x + skip; w < cnt * AW; w += B) q[lo * AW + w - AW] = st[w];
+}
+
+// out_i = sum_j c_j p_(j,i), i < n_out (an input shorter than i + 1 contributes nothing); ABI Montgomery in and out.  The k
+// coefficients enter the device image once per workgroup, through LDS, B at a time.  out may alias an input.
+template <class F>
+__global__ void __launch_bounds__(256) poly_lincomb(const PolyDesc* __restrict__ descs, const uint32_t* __restrict__ coeffs_abi,
+                                                    uint32_t k, uint64_t n_out, uint32_t* out) {
+  constexpr int B = 256, AW = F::ABI_WORDS;
+  __shared__ __attribute__((aligned(16))) uint32_t cs[B * F::WORDS];
+  const uint64_t i = (uint64_t)blockIdx.x * B + threadIdx.x;
+  F acc = F::zero();
+  for (uint32_t j0 = 0; j0 < k; j0 += B) {
+    __syncthreads();
+    if (j0 + threadIdx.x < k) F::from_abi(coeffs_abi + (size_t)(j0 + threadIdx.x) * AW).store(cs + (size_t)threadIdx.x * F::WORDS);
+    __syncthreads();
+    const uint32_t je = min(k, j0 + B);
+    for (uint32_t j = j0; j < je; j++) {
+      const PolyDesc d = descs[j];
+      if (i < d.len) acc = acc + F::load(cs + (size_t)(j - j0) * F::WORDS) * F::unpack32(d.p + i * AW);
+    }
+  }
+  if (i < n_out) acc.canonical().pack32(out + i * AW);
+}
+
+}  // namespace pcd
