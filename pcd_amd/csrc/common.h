@@ -46,7 +46,7 @@ struct pcdhip_bases {
   std::vector<size_t> shard_lo;
 };
 namespace pcd {
-// One constraint matrix on the device (built by upload_csr_to, capi.hip).  Inside every row the entries whose coefficient is a SMALL
+// One constraint matrix on the device (built by upload_csr_to, capi_witness.hip).  Inside every row the entries whose coefficient is a SMALL
 // integer (|c| <= 32: the +-1 of linear combinations and booleanity constraints, the 2, 3, 4 of range checks -- most of what
 // `cs.finalize()` leaves in a verifier circuit) come first: `nl[r]` of them, coefficient in `lc` (int8); the others follow with
 // their coefficients as field elements (device image) in `coeff` (indexed like col; the slots of light entries are unused).  Rows with
@@ -136,7 +136,7 @@ struct pcdhip_ctx {
   int g16_schedule = 0;             // pcdhip_groth16_set_schedule: 0 assignment MSMs first, the map under them (default: fastest, measured again in round 5); 1 the map first, then all MSMs at once; 2 the map first, then the accumulate lane
   // the accumulate lane (msm.hip.h MsmLane; schedule 2 only): one stream confined by a CU mask to all but `lane_reserve` compute units, for
   // the accumulate kernels of the MSMs that share the device (a proof's five; submitted MSMs).  The masked stream comes from a process-wide
-  // pool and is never destroyed (capi.hip masked_lane_of); `lane_stream` is the owned, unmasked one of reserve 0.
+  // pool and is never destroyed (capi_msm.hip masked_lane_of); `lane_stream` is the owned, unmasked one of reserve 0.
   hipStream_t lane_stream = nullptr;
   pcd::MsmLane lane;
   int lane_reserve = -1;            // CUs the lane leaves to the other streams (pcdhip_set_lane_reserve; -1: default, PCDHIP_LANE_RESERVE or 8; 0: no mask)

@@ -3,7 +3,7 @@
 //   A = alpha + a_query[0] + r*delta + M_a          B = beta + b_query[0] + s*delta + M_b   (G1 and G2)
 //   C = s*A + r*B_1 - r s*delta + M_l + M_h  =  s*(alpha + a_0 + M_a) + r*(beta_1 + b_0 + M_b1) + r s*delta + M_l + M_h
 // The two variable-base products s*A and r*B_1 are either folded into MSMs (below) or computed by one lane each on the
-// stream of the MSM that produced the point, where they overlap the longer MSMs of the same proof (capi.hip).
+// stream of the MSM that produced the point, where they overlap the longer MSMs of the same proof (capi_g16_prove.hip).
 #include "common.h"
 
 namespace pcd {

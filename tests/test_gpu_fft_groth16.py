@@ -151,7 +151,7 @@ def test_witness_map_skewed_matrix(co, gpu_ctx, cid, nc):
 def test_prove_keys_with_points_at_infinity(co, gpu_ctx, cid, nc):
     """The a / b queries of a real key hold the point at infinity for every variable that no row of A / B mentions (a third of them in
     this R1CS).  Their entries are left out of the MSMs' bucket lists, and which MSMs of a proof share a sort depends on them
-    (capi.hip G16Run::launch_assignment): the key as a setup makes it, the key with every entry finite, and a key whose b_g1 / b_g2 flags
+    (capi_g16_prove.hip G16Run::launch_assignment): the key as a setup makes it, the key with every entry finite, and a key whose b_g1 / b_g2 flags
     differ, each through both assembly forms -- the proof equal to the oracle's every time.  (Whatever coordinates a flagged entry holds
     are ignored: the synthetic key keeps its seeded points there.)"""
     fr = co.CURVE_FR[cid]
