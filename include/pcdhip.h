@@ -452,6 +452,28 @@ int pcdhip_kzg_check(pcdhip_ctx* ctx, int curve_id, const uint64_t* g_xy, const 
                      const uint64_t* values_mont, const uint64_t* w_xy, const uint8_t* w_inf, const uint64_t* random_v_mont,
                      const uint64_t* randomizers_canonical, int* ok);
 
+/* ---- K8 vector algebra for Marlin's AHP rounds ---------------------------------------------------------------------------
+ * What the prover does with a polynomial between its transforms and its commitments, on device vectors of ABI Montgomery elements.
+ * All buffers of one call are of the same field and a count may not exceed a buffer's n (PCDHIP_E_ARG otherwise, as for null
+ * pointers).  Everything runs on the context's own stream and workspaces, which MSM tickets do not use; a multi-device context
+ * addresses its device 0. */
+/* the pointwise product: out_i = a_i b_i for i < n (out may be a or b, and a may be b) */
+int pcdhip_vec_mul(pcdhip_ctx* ctx, const pcdhip_buf* a, const pcdhip_buf* b, size_t n, pcdhip_buf* out);
+/* ark-ff `batch_inversion` (scale_mont == NULL) / `batch_inversion_and_mul`: out_i = scale / in_i for in_i != 0 and out_i = 0 for
+ * in_i == 0 (upstream leaves zeros in place).  Montgomery's trick per tile of the vector, one kernel; out may be in; n == 0 is fine. */
+int pcdhip_vec_batch_inverse(pcdhip_ctx* ctx, const pcdhip_buf* in, size_t n, const uint64_t* scale_mont, pcdhip_buf* out);
+/* ark-poly `DensePolynomial::divide_by_vanishing_poly`: the unique q, r with p = q (X^domain_n - 1) + r and deg r < domain_n, for any
+ * domain_n >= 1 (not only domain sizes).  *q_len = len > domain_n ? len - domain_n : 0 coefficients of q, *r_len = min(len, domain_n)
+ * of r; r and r_len may be NULL, q may be NULL when *q_len == 0.  q and r must not be p's buffer nor each other.  One lane per
+ * coefficient sums its stride-domain_n column of p: a single streaming pass for len up to a few domain_n, and a cost that grows with
+ * len / domain_n beyond that. */
+int pcdhip_poly_div_vanishing(pcdhip_ctx* ctx, const pcdhip_buf* p, size_t len, size_t domain_n, pcdhip_buf* q, size_t* q_len,
+                              pcdhip_buf* r, size_t* r_len);
+/* ark-poly `&DensePolynomial * &DensePolynomial`: *out_len = la + lb - 1 coefficients (0 when la == 0 or lb == 0), NOT trimmed of
+ * leading zeros as upstream's result is.  Two forward transforms, a pointwise product and an inverse transform over the domain
+ * pcdhip_domain_size(field, la + lb - 1); PCDHIP_E_SIZE_UNSUPPORTED when that is 0.  out may be a or b. */
+int pcdhip_poly_mul(pcdhip_ctx* ctx, const pcdhip_buf* a, size_t la, const pcdhip_buf* b, size_t lb, pcdhip_buf* out, size_t* out_len);
+
 /* ---- timing helpers (HIP events on the context's stream, for bench.py) ------------------------- */
 int pcdhip_timer_start(pcdhip_ctx* ctx);
 int pcdhip_timer_stop(pcdhip_ctx* ctx, float* out_ms);

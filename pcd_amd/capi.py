@@ -62,6 +62,7 @@ EXPORTS = [
     "pcdhip_process_vk", "pcdhip_pvk_free", "pcdhip_groth16_verify_prepared", "pcdhip_groth16_verify_batch_rlc",
     "pcdhip_multi_pairing", "pcdhip_pairing_set_mode", "pcdhip_groth16_verify", "pcdhip_groth16_verify_batch", "pcdhip_timer_start", "pcdhip_timer_stop",
     "pcdhip_poly_eval", "pcdhip_poly_lincomb", "pcdhip_poly_div_linear", "pcdhip_kzg_open", "pcdhip_kzg_check",
+    "pcdhip_vec_mul", "pcdhip_vec_batch_inverse", "pcdhip_poly_div_vanishing", "pcdhip_poly_mul",
 ]
 
 
@@ -81,6 +82,11 @@ def lib():
             getattr(_LIB, name).restype = C.c_size_t
         for name in ("pcdhip_buf_free", "pcdhip_bases_free", "pcdhip_g16_pk_free", "pcdhip_host_free", "pcdhip_pvk_free"):
             getattr(_LIB, name).restype = None
+        vp, sz, szp = C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)
+        _LIB.pcdhip_vec_mul.argtypes = [vp, vp, vp, sz, vp]
+        _LIB.pcdhip_vec_batch_inverse.argtypes = [vp, vp, sz, vp, vp]
+        _LIB.pcdhip_poly_div_vanishing.argtypes = [vp, vp, sz, sz, vp, szp, vp, szp]
+        _LIB.pcdhip_poly_mul.argtypes = [vp, vp, sz, vp, sz, vp, szp]
     return _LIB
 
 
@@ -559,6 +565,65 @@ class Context:
             q.free()
         self._check(rc)
         return q, v
+
+    # ---- K8: vector algebra for Marlin's AHP rounds
+    def buf_alloc(self, field, n):
+        h = C.c_void_p()
+        self._check(lib().pcdhip_buf_alloc(self._ctx, field, C.c_size_t(n), C.byref(h)))
+        return DeviceBuf(self, h, field, n)
+
+    def _call_into(self, own, fn):
+        """fn() -> rc; the buffers of `own` (allocated for this call) are freed when it fails"""
+        rc = fn()
+        if rc:
+            for b in own:
+                b.free()
+        self._check(rc)
+
+    def vec_mul(self, a, b, n=None, out=None):
+        """out_i = a_i b_i for i < n (default: the shorter vector) -> out (allocated when not passed; may be a or b)"""
+        n = min(a.n, b.n) if n is None else int(n)
+        own = [] if out is not None else [self.buf_alloc(a.field, n)]
+        out = out if out is not None else own[0]
+        self._call_into(own, lambda: lib().pcdhip_vec_mul(self._ctx, a._h, b._h, n, out._h))
+        return out
+
+    def vec_batch_inverse(self, x, n=None, scale_mont=None, out=None):
+        """ark-ff batch_inversion / batch_inversion_and_mul: out_i = scale / x_i, zeros stay zero -> out (may be x)"""
+        n = x.n if n is None else int(n)
+        own = [] if out is not None else [self.buf_alloc(x.field, n)]
+        out = out if out is not None else own[0]
+        sc = _p(_u64(scale_mont)) if scale_mont is not None else None
+        self._call_into(own, lambda: lib().pcdhip_vec_batch_inverse(self._ctx, x._h, n, sc, out._h))
+        return out
+
+    def poly_div_vanishing(self, p, domain_n, length=None, q=None, r=None, want_r=True):
+        """p = q (X^domain_n - 1) + r -> (q, q_len, r, r_len); q is None when there is no quotient, r is None with want_r=False"""
+        length = p.n if length is None else int(length)
+        domain_n = int(domain_n)
+        ql, rl = max(length - domain_n, 0), min(length, domain_n)
+        own = []
+        if q is None and ql:
+            q = self.buf_alloc(p.field, ql)
+            own.append(q)
+        if r is None and want_r:
+            r = self.buf_alloc(p.field, rl)
+            own.append(r)
+        qn, rn = C.c_size_t(0), C.c_size_t(0)
+        self._call_into(own, lambda: lib().pcdhip_poly_div_vanishing(self._ctx, p._h, length, domain_n, q._h if q is not None else None,
+                                                                     C.byref(qn), r._h if r is not None else None,
+                                                                     C.byref(rn) if r is not None else None))
+        return q, qn.value, r, (rn.value if r is not None else None)
+
+    def poly_mul(self, a, b, la=None, lb=None, out=None):
+        """ark-poly &a * &b -> (out, la + lb - 1 coefficients, not trimmed; 0 when an operand is empty); out may be a or b"""
+        la = a.n if la is None else int(la)
+        lb = b.n if lb is None else int(lb)
+        own = [] if out is not None else [self.buf_alloc(a.field, la + lb - 1 if la and lb else 0)]
+        out = out if out is not None else own[0]
+        n = C.c_size_t(0)
+        self._call_into(own, lambda: lib().pcdhip_poly_mul(self._ctx, a._h, la, b._h, lb, out._h, C.byref(n)))
+        return out, n.value
 
     def kzg_open(self, powers_of_g, p, z_mont, length=None, powers_of_gamma_g=None, blinding=None, blinding_len=None):
         """KZG10::open -> (w Jacobian X||Y||Z, p(z), blinding(z) or None when there is no blinding polynomial)"""

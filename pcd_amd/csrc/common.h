@@ -231,6 +231,13 @@ struct FieldEntry {
                           uint32_t* values_abi_dev, const PolyDesc* div, uint32_t* q_out, int q_canonical);
   // out_i = sum_j c_j p_(j,i) for i < n_out (C-ABI Montgomery everywhere; coeffs_abi_dev on the device; out may alias an input)
   hipError_t (*poly_lincomb)(hipStream_t, const PolyDesc* descs_dev, const uint32_t* coeffs_abi_dev, uint32_t k, uint64_t n_out, uint32_t* out);
+  // K8 vector algebra (poly.hip.h), C-ABI Montgomery vectors on the device.  vec_mul: out_i = a_i b_i (out may be a or b); with abi == 0
+  // the three vectors are in the device image instead (the pointwise step of a polynomial product)
+  hipError_t (*vec_mul)(hipStream_t, const uint32_t* a, const uint32_t* b, uint64_t n, uint32_t* out, int abi);
+  // out_i = scale / in_i, zeros stay zero; scale_abi: C-ABI words on the host, or null for 1; out may be in
+  hipError_t (*vec_batch_inverse)(hipStream_t, const uint32_t* in, uint64_t n, const uint32_t* scale_abi, uint32_t* out);
+  // p = q (X^n - 1) + r: len - n coefficients of q (none for len <= n), min(len, n) of r (r may be null); q, r distinct from p
+  hipError_t (*poly_div_vanishing)(hipStream_t, const uint32_t* p, uint64_t len, uint64_t n, uint32_t* q, uint32_t* r);
 };
 const FieldEntry& field_entry(int field_id);
 

@@ -494,6 +494,32 @@ hipError_t poly_lincomb_run(hipStream_t st, const PolyDesc* descs_dev, const uin
   return hipGetLastError();
 }
 
+// ---- K8 vector algebra (poly.hip.h): batch inversion, pointwise product, division by X^n - 1
+hipError_t vec_mul_run(hipStream_t st, const uint32_t* a, const uint32_t* b, uint64_t n, uint32_t* out, int abi) {
+  if (n == 0) return hipSuccess;
+  const dim3 gd((uint32_t)((n + 255) / 256)), bd(256);
+  if (abi) hipLaunchKernelGGL((poly_vec_mul<FTP, true>), gd, bd, 0, st, a, b, n, out);
+  else hipLaunchKernelGGL((poly_vec_mul<FTP, false>), gd, bd, 0, st, a, b, n, out);
+  return hipGetLastError();
+}
+hipError_t vec_batch_inverse_run(hipStream_t st, const uint32_t* in, uint64_t n, const uint32_t* scale_abi, uint32_t* out) {
+  if (n == 0) return hipSuccess;
+  constexpr bool LANE_INV = PCD_BINV_LANE_INV != 0;
+  typedef BinvCfg<FTP, LANE_INV> BC;
+  PolyAbiElt<FTP> s;
+  memset(s.w, 0, sizeof s.w);
+  if (scale_abi) memcpy(s.w, scale_abi, sizeof s.w);
+  hipLaunchKernelGGL((poly_batch_inv_tile<FTP, LANE_INV>), dim3((uint32_t)((n + BC::TILE - 1) / BC::TILE)), dim3(BC::B), 0, st, in, n, s,
+                     scale_abi ? 1 : 0, out);
+  return hipGetLastError();
+}
+hipError_t poly_div_vanishing_run(hipStream_t st, const uint32_t* p, uint64_t len, uint64_t n, uint32_t* q, uint32_t* r) {
+  const uint64_t lanes = std::max<uint64_t>(len > n ? len - n : 0, r ? std::min<uint64_t>(len, n) : 0);
+  if (lanes == 0) return hipSuccess;
+  hipLaunchKernelGGL(poly_div_vanishing<FTP>, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, st, p, len, n, q, r);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 #define PCD_CAT_(a, b) a##b
@@ -501,7 +527,8 @@ hipError_t poly_lincomb_run(hipStream_t st, const PolyDesc* descs_dev, const uin
 const FieldEntry* PCD_CAT(pcd_field_entry_, PCD_FIELD_IDX)() {
   static const FieldEntry e = {EW, FT::ABI_WORDS, FT::Params::TWO_ADICITY, make_tables, run, convert, spmv, small_abi, mul_sub_divz,
                                mixed_make_tables, mixed_run, mixed_mul_sub_divz, scale_canon, SETUP_CONSTS, setup_scalars, run_batched_entry, spmv3,
-                               poly_scratch_words, poly_eval, poly_lincomb_run};
+                               poly_scratch_words, poly_eval, poly_lincomb_run, vec_mul_run, vec_batch_inverse_run,
+                               poly_div_vanishing_run};
   return &e;
 }
 

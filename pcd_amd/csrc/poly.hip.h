@@ -206,4 +206,125 @@ __global__ void __launch_bounds__(256) poly_lincomb(const PolyDesc* __restrict__
   if (i < n_out) acc.canonical().pack32(out + i * AW);
 }
 
+// ---- K8, vector algebra for Marlin's AHP rounds: batch inversion (ark-ff `batch_inversion[_and_mul]`), the pointwise product, division
+// by the vanishing polynomial X^n - 1 (ark-poly `divide_by_vanishing_poly`).  ABI Montgomery words in and out, as above.
+//
+// Batch inversion: Montgomery's trick at two levels.  A tile of B x E elements is staged through LDS; a lane owns E consecutive
+// elements, replaces zeros by one (remembered in a bit mask), and leaves its running products P_k = x_0 .. x_k in the slots of the
+// x_k.  The lane products are inverted -- one inv_gcd per lane (LANE_INV), or one per workgroup over a prefix and a suffix product scan
+// of the lanes -- and the walk back down turns slot k into inv * P_(k-1) and inv into inv * x_k, with x_k read again from `in` (the lines
+// the workgroup has just staged; nothing of the tile is stored before the walk has ended, so out may be in).  3 (E - 1) products per
+// lane besides the inversion's share.
+// The R factors: unpack32 reads x R as the device image of x rho, rho = R / R'.  P_k carries rho^(k+1), the inverse of the lane product
+// rho^-E, so inv * P_(k-1) is the device image of x_k^-1 / rho: the integer x_k^-1 R'^2 / R.  The constant K = scale R^2 / R' folded
+// into the lane inverse once (unpack32(scale R) * cout, cout = R; cout * cout without a scale) makes that scale x_k^-1 R, the ABI image.
+#ifndef PCD_BINV_LANE_INV
+#define PCD_BINV_LANE_INV 1
+#endif
+template <class F, bool LANE_INV = (PCD_BINV_LANE_INV != 0)>
+struct BinvCfg {  // LDS: the tile in ABI words + one pad word per lane (+ B elements for the scans)
+  static constexpr int B = LANE_INV ? 64 : 128;
+  static constexpr int E = LANE_INV ? (F::N <= 11 ? 16 : 8) : (F::N <= 11 ? 8 : 4);
+  static constexpr uint32_t TILE = (uint32_t)B * E;
+};
+
+template <class F, bool LANE_INV>
+__global__ void __launch_bounds__((BinvCfg<F, LANE_INV>::B)) poly_batch_inv_tile(const uint32_t* in, uint64_t n, const PolyAbiElt<F> scale_abi,
+                                                                               int has_scale, uint32_t* out) {
+  typedef BinvCfg<F, LANE_INV> Cfg;
+  constexpr int B = Cfg::B, E = Cfg::E, AW = F::ABI_WORDS;
+  constexpr uint32_t TILE = Cfg::TILE, CHUNK = (uint32_t)E * AW;  // a lane's chunk starts at t (CHUNK + 1): odd stride, no bank shared
+  __shared__ __attribute__((aligned(16))) uint32_t st[TILE * AW + B];
+  __shared__ __attribute__((aligned(16))) uint32_t red[LANE_INV ? 1 : B * F::WORDS];
+  const uint32_t t = threadIdx.x;
+  const uint64_t lo = (uint64_t)blockIdx.x * TILE;
+  const uint32_t cnt = (uint32_t)(n - lo < TILE ? n - lo : TILE);
+  const uint32_t* src = in + lo * AW;
+  for (uint32_t w = t; w < TILE * AW; w += B) st[w + w / CHUNK] = w < cnt * AW ? src[w] : 0u;
+  F cout;
+#pragma unroll
+  for (int i = 0; i < F::N; i++) cout.v[i] = F::Params::cout(i);
+  const F K = (has_scale ? F::unpack32(scale_abi.w) : cout) * cout;
+  __syncthreads();
+  uint32_t* mine = st + (size_t)t * (CHUNK + 1);
+  uint32_t zmask = 0;
+  F run = F::one();
+#pragma unroll 1
+  for (int k = 0; k < E; k++) {
+    uint32_t* s = mine + k * AW;
+    F x = F::unpack32(s);
+    if (x.is_zero()) { zmask |= 1u << k; x = F::one(); }
+    run = k == 0 ? x : run * x;
+    run.canonical().pack32(s);
+  }
+  F inv;
+  if constexpr (LANE_INV) {
+    inv = run.inv() * K;
+  } else {
+    // 1 / L_t = (1 / total) * (L_0 .. L_(t-1)) * (L_(t+1) .. L_(B-1)): an inclusive prefix and an inclusive suffix product scan of the
+    // lanes through the one array, each lane keeping its neighbour's value
+    F pre = run, suf = run;
+    for (int d = 1; d < B; d <<= 1) {
+      pre.store(red + (size_t)t * F::WORDS);
+      __syncthreads();
+      if (t >= (uint32_t)d) pre = pre * F::load(red + (size_t)(t - d) * F::WORDS);
+      __syncthreads();
+    }
+    pre.store(red + (size_t)t * F::WORDS);
+    __syncthreads();
+    const F below = t > 0 ? F::load(red + (size_t)(t - 1) * F::WORDS) : F::one();
+    __syncthreads();
+    for (int d = 1; d < B; d <<= 1) {
+      suf.store(red + (size_t)t * F::WORDS);
+      __syncthreads();
+      if (t + d < (uint32_t)B) suf = suf * F::load(red + (size_t)(t + d) * F::WORDS);
+      __syncthreads();
+    }
+    suf.store(red + (size_t)t * F::WORDS);
+    __syncthreads();
+    const F above = t + 1 < (uint32_t)B ? F::load(red + (size_t)(t + 1) * F::WORDS) : F::one();
+    __syncthreads();
+    if (t == B - 1) (pre.inv() * K).store(red);
+    __syncthreads();
+    inv = F::load(red) * below * above;
+  }
+  const uint32_t* again = src + (size_t)t * CHUNK;
+#pragma unroll 1
+  for (int k = E - 1; k >= 0; k--) {
+    uint32_t* s = mine + k * AW;
+    const bool z = (zmask >> k) & 1u;  // (a zero, or the padding behind the vector's end: never read again)
+    const F y = k > 0 ? inv * F::unpack32(s - AW) : inv;
+    if (k > 0) inv = inv * (z ? F::one() : F::unpack32(again + k * AW));
+    (z ? F::zero() : y.canonical()).pack32(s);
+  }
+  __syncthreads();
+  uint32_t* dst = out + lo * AW;
+  for (uint32_t w = t; w < cnt * AW; w += B) dst[w] = st[w + w / CHUNK];
+}
+
+// out_i = a_i b_i, i < n.  ABI: from_abi puts one operand into the device image, the other is read as it stands (b R), so the product is
+// a b R, the ABI image.  !ABI: device image in and out (the pointwise step of the polynomial product, between its transforms).
+template <class F, bool ABI>
+__global__ void __launch_bounds__(256) poly_vec_mul(const uint32_t* a, const uint32_t* b, uint64_t n, uint32_t* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  if constexpr (ABI) (F::from_abi(a + i * F::ABI_WORDS) * F::unpack32(b + i * F::ABI_WORDS)).canonical().pack32(out + i * F::ABI_WORDS);
+  else (F::load(a + i * F::WORDS) * F::load(b + i * F::WORDS)).store(out + i * F::WORDS);
+}
+
+// p = q (X^n - 1) + r: q_j = sum_{i >= 1, j + i n < len} p_(j + i n) for j < q_len = len - n, r_j = p_j + q_j for j < min(len, n)
+// (r may be null).  Lane j walks its column with stride n: one streaming pass for len <= a few n, len / n terms per lane in general.
+template <class F>
+__global__ void __launch_bounds__(256) poly_div_vanishing(const uint32_t* __restrict__ p, uint64_t len, uint64_t n, uint32_t* __restrict__ q,
+                                                          uint32_t* __restrict__ r) {
+  constexpr int AW = F::ABI_WORDS;
+  const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t q_len = len > n ? len - n : 0, r_len = len < n ? len : n;
+  if (j >= q_len && j >= r_len) return;
+  F acc = F::zero();
+  for (uint64_t i = j + n; i < len; i += n) acc = acc + F::unpack32(p + i * AW);
+  if (j < q_len) acc.canonical().pack32(q + j * AW);
+  if (r && j < r_len) (acc + F::unpack32(p + j * AW)).canonical().pack32(r + j * AW);
+}
+
 }  // namespace pcd

@@ -68,6 +68,13 @@ extern "C" {
                                           proofs: *const u64, proofs_inf: *const u8, ok: *mut c_int) -> c_int;
     pub fn pcdhip_groth16_verify_batch_rlc(ctx: *mut pcdhip_ctx, pvk: *const pcdhip_pvk, n_proofs: usize, public_inputs: *const u64,
                                            proofs: *const u64, proofs_inf: *const u8, rho: *const u64, all_ok: *mut c_int) -> c_int;
+    // K8: vector algebra for Marlin's AHP rounds (batch_inversion[_and_mul], pointwise product, divide_by_vanishing_poly, &p * &q)
+    pub fn pcdhip_vec_mul(ctx: *mut pcdhip_ctx, a: *const pcdhip_buf, b: *const pcdhip_buf, n: usize, out: *mut pcdhip_buf) -> c_int;
+    pub fn pcdhip_vec_batch_inverse(ctx: *mut pcdhip_ctx, input: *const pcdhip_buf, n: usize, scale_mont: *const u64, out: *mut pcdhip_buf) -> c_int;
+    pub fn pcdhip_poly_div_vanishing(ctx: *mut pcdhip_ctx, p: *const pcdhip_buf, len: usize, domain_n: usize, q: *mut pcdhip_buf, q_len: *mut usize,
+                                     r: *mut pcdhip_buf, r_len: *mut usize) -> c_int;
+    pub fn pcdhip_poly_mul(ctx: *mut pcdhip_ctx, a: *const pcdhip_buf, la: usize, b: *const pcdhip_buf, lb: usize, out: *mut pcdhip_buf,
+                           out_len: *mut usize) -> c_int;
 }
 
 /// `PCDHIP_E_*` (include/pcdhip.h)
