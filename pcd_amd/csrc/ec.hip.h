@@ -388,8 +388,8 @@ struct EC {
   // reduced Jacobian form this replaces.  Bounds (value as a multiple of p | needed for a product: ca cb <= 1024; limb products
   // per column < 2^63):
   //   P = U2 - X1 + 16p < 18p (carried)   R = S2 - Y1 + 4p < 6p (carried)   PP, R^2, PPP, Q < 2p
-  //   X3 = R^2 - PPP - 2Q + 8p in (2p, 10p) (carried)   t = Q - X3 + 16p in (6p, 18p), limbs in (-2^28, 1.25 * 2^30)
-  //   Y1' = 4p - Y1 in (2p, 4p]   Y3 = R t + Y1' PPP: 6 * 18 + 4 * 2 = 116;  columns < 11 (2^28 * 1.25 * 2^30 + 2^29 * 2^28) + 11 * 2^56 < 2^62
+  //   X3 = R^2 - PPP - 2Q + 8p in (2p, 10p) (carried)   t = Q - X3 + 16p in (6p, 18p) (below 16p in fact: X3 > 2p), limbs in (-2^28, 1.25 * 2^30)
+  //   Y1' = 4p - Y1 in (2p, 4p]   Y3 = R t + Y1' PPP: 6 * 18 + 4 * 2 = 116 (6 * 16 + 8 = 104 reached);  columns < 11 (2^28 * 1.25 * 2^30 + 2^29 * 2^28) + 11 * 2^56 < 2^62
   struct AccLz {
     typename F::Lz X;
     F Y, ZZ, ZZZ;

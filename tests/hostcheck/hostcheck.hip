@@ -141,3 +141,74 @@ extern "C" int hc_maddx_chain(int group_idx, const uint32_t* bases, int n, uint3
   return 0;
 }
 
+// ---- one operation per element on RAW limb images, the same per-element code the gfx950 harness runs (tests/gpucheck/fieldops_ops.h):
+// tests/test_field_ops_host.py feeds the case lists of tests/field_reference.py and checks against Python integers.  variant 0: the
+// inlined products, 1: the non-inlined mul_call / sqr_call bodies (753-bit fields only; the mailbox form exists on the device alone).
+// `ran` counts the elements processed.
+#include "../gpucheck/fieldops_ops.h"
+template <class F>
+static void field_case_ops(int op, const uint32_t* a, const uint32_t* b, uint32_t k, int n, uint32_t* out, uint32_t* ran) {
+  const int sa = fieldops::field_a_words<F>(op, k), sb = fieldops::field_b_words<F>(op, k);
+  for (int i = 0; i < n; i++) { fieldops::field_op<F>(op, a + (size_t)i * sa, b + (size_t)i * sb, k, out + (size_t)i * F::N); ++*ran; }
+}
+extern "C" int hc_field_case_ops(int field, int variant, int op, const uint32_t* a, const uint32_t* b, uint32_t k, int n, uint32_t* out,
+                                 uint32_t* ran) {
+  if (op < 0 || op >= fieldops::F_OPS || (op == fieldops::F_SIGNED_SUM && k > fieldops::SIGNED_SUM_MAX_TERMS)) return -1;
+  if (field < 0 || field > 3 || variant < 0 || variant > (field < 2 ? 0 : 1)) return -1;
+  switch (field * 2 + variant) {
+    case 0: field_case_ops<Fp<F298A, true>>(op, a, b, k, n, out, ran); break;
+    case 2: field_case_ops<Fp<F298B, true>>(op, a, b, k, n, out, ran); break;
+    case 4: field_case_ops<Fp<F753A, true>>(op, a, b, k, n, out, ran); break;
+    case 5: field_case_ops<Fp<F753A, false>>(op, a, b, k, n, out, ran); break;
+    case 6: field_case_ops<Fp<F753B, true>>(op, a, b, k, n, out, ran); break;
+    case 7: field_case_ops<Fp<F753B, false>>(op, a, b, k, n, out, ran); break;
+    default: return -1;
+  }
+  return 0;
+}
+template <class F>
+static void lz_ops(int op, const int32_t* ops, int32_t k, int n, uint32_t* out, uint32_t* ran) {
+  for (int i = 0; i < n; i++) { fieldops::lz_op<F>(op, ops + (size_t)i * 8 * F::N, k, out + (size_t)i * F::N); ++*ran; }
+}
+extern "C" int hc_lz_ops(int field, int op, const int32_t* ops, int32_t k, int n, uint32_t* out, uint32_t* ran) {
+  if (op < 0 || op >= fieldops::L_OPS) return -1;
+  switch (field) {
+    case 0: lz_ops<Fp<F298A, true>>(op, ops, k, n, out, ran); break;
+    case 1: lz_ops<Fp<F298B, true>>(op, ops, k, n, out, ran); break;
+    default: return -1;
+  }
+  return 0;
+}
+template <class T>
+static void tower_ops(int op, const uint32_t* a, const uint32_t* b, int n, uint32_t* out, uint32_t* ran) {
+  for (int i = 0; i < n; i++) { fieldops::tower_op<T>(op, a + (size_t)i * T::WORDS, b + (size_t)i * T::WORDS, out + (size_t)i * T::WORDS); ++*ran; }
+}
+extern "C" int hc_tower_ops(int field, int op, const uint32_t* a, const uint32_t* b, int n, uint32_t* out, uint32_t* ran) {
+  if (op < 0 || op >= fieldops::T_OPS) return -1;
+  switch (field) {
+    case 0: tower_ops<fieldops::Tower0>(op, a, b, n, out, ran); break;
+    case 1: tower_ops<fieldops::Tower1>(op, a, b, n, out, ran); break;
+    case 2: tower_ops<fieldops::Tower2>(op, a, b, n, out, ran); break;
+    case 3: tower_ops<fieldops::Tower3>(op, a, b, n, out, ran); break;
+    default: return -1;
+  }
+  return 0;
+}
+// `steps` mixed additions per element from a raw accumulator record (X || Y || ZZ || ZZZ || identity flag), points q[element][step]
+template <class G>
+static int madd_step(int op, const uint32_t* acc, const uint32_t* q, int steps, int n, uint32_t* out, uint32_t* ran) {
+  if (op == fieldops::S_MADD_LZ && !LazyCapable<typename G::F>::value) return -1;
+  constexpr int SW = fieldops::step_words<G>(), QW = 2 * G::F::WORDS;
+  for (int i = 0; i < n; i++) { fieldops::madd_steps<G>(op, acc + (size_t)i * SW, q + (size_t)i * steps * QW, steps, out + (size_t)i * SW); ++*ran; }
+  return 0;
+}
+extern "C" int hc_madd_step(int curve, int grp, int op, const uint32_t* acc, const uint32_t* q, int steps, int n, uint32_t* out, uint32_t* ran) {
+  if (op < 0 || op >= fieldops::S_OPS) return -1;
+  switch (curve * 2 + grp - 1) {
+    case 0: return madd_step<G1_MNT4_298>(op, acc, q, steps, n, out, ran);
+    case 1: return madd_step<G2_MNT4_298>(op, acc, q, steps, n, out, ran);
+    case 2: return madd_step<G1_MNT6_298>(op, acc, q, steps, n, out, ran);
+    case 3: return madd_step<G2_MNT6_298>(op, acc, q, steps, n, out, ran);
+    default: return -1;
+  }
+}

@@ -44,6 +44,60 @@ def test_mixed_radix_fft(co, gpu_ctx, fid, q):
         gpu_ctx.fft_general(fid, np.zeros((3 * 64, x.shape[1]), dtype=np.uint64))  # 3 * 2^6 is not a domain size
 
 
+def _structured_inputs(fid, n):
+    """all zero, all p - 1, a delta at index 0 and at index n - 1, a constant c, alternating 0 / p - 1 (C-ABI Montgomery images);
+    the butterflies of the other FFT tests only ever see random residues"""
+    from oracle import pyoracle as O
+    f = O.FIELDS[fid]
+    c = (f.p - 1) // 3 + 5
+    row = lambda v: O.pack_fp(f, [v])[0]
+    zero, top, one, cst = row(0), row(f.p - 1), row(1), row(c)
+    full = lambda r: np.ascontiguousarray(np.tile(r, (n, 1)))
+    d0, dn, alt = full(zero), full(zero), full(zero)
+    d0[0] = one
+    dn[n - 1] = one
+    alt[1::2] = top
+    return {"zero": full(zero), "p-1": full(top), "delta0": d0, "delta_last": dn, "const": full(cst), "alt": alt}, c
+
+
+# one log_n per kernel path (fft.hip.h): a single pass up to 10 -- 0 and 1 are the degenerate and the smallest transform (no twiddled layer);
+# 9 and 10 are the sizes at which fft_pass_kernel renormalises the lazily reduced 298-bit elements (blog > 8 in the one-layer loop, blog > 7
+# in the two-layer loop: unreduced values stack 8 - 9 layers deep only there, and 2^10 is the largest LDS tile) -- two passes from 11, three from 15
+@pytest.mark.parametrize("log_n", [0, 1, 9, 10, 11, 15])
+@pytest.mark.parametrize("fid", [0, 1, 2, 3])
+def test_fft_structured_vectors(co, gpu_ctx, fid, log_n):
+    from oracle import pyoracle as O
+    f = O.FIELDS[fid]
+    n = 1 << log_n
+    ins, c = _structured_inputs(fid, n)
+    for name, x in ins.items():
+        for inv in (False, True):
+            for coset in (False, True):
+                got = gpu_ctx.fft(fid, x, inverse=inv, coset=coset)
+                assert np.array_equal(got, co.fft(fid, x, inverse=inv, coset=coset, nthreads=16)), (fid, log_n, name, inv, coset)
+                if not inv and not coset and name == "delta0":     # closed forms, in Python integers: all ones
+                    assert np.array_equal(got, np.tile(O.pack_fp(f, [1])[0], (n, 1))), (fid, log_n, name)
+                if not inv and not coset and name == "const":      # n c at index 0, zero elsewhere
+                    assert O.unpack_fp(f, got[:1])[0] == n * c % f.p and not got[1:].any(), (fid, log_n, name)
+
+
+@pytest.mark.parametrize("fid,m", [(0, 7), (2, 5)])
+def test_mixed_radix_fft_structured_vectors(co, gpu_ctx, fid, m):
+    from oracle import pyoracle as O
+    f = O.FIELDS[fid]
+    n = m << 3
+    ins, c = _structured_inputs(fid, n)
+    for name, x in ins.items():
+        for inv in (False, True):
+            for coset in (False, True):
+                got = gpu_ctx.fft_general(fid, x, inverse=inv, coset=coset)
+                assert np.array_equal(got, co.fft_general(fid, x, m, inverse=inv, coset=coset, nthreads=16)), (fid, m, name, inv, coset)
+                if not inv and not coset and name == "delta0":
+                    assert np.array_equal(got, np.tile(O.pack_fp(f, [1])[0], (n, 1))), (fid, m, name)
+                if not inv and not coset and name == "const":
+                    assert O.unpack_fp(f, got[:1])[0] == n * c % f.p and not got[1:].any(), (fid, m, name)
+
+
 @pytest.mark.parametrize("fid,n", [(1, 1 << 12), (3, 1 << 9), (0, 7 << 6), (2, 25 << 4)])
 def test_fft_seq_one_round_trip(co, gpu_ctx, fid, n):
     """pcdhip_fft_seq (seam S2: a chain of transforms on one host vector, one trip over PCIe) == the same transforms one call at a time ==

@@ -6,12 +6,14 @@ import ctypes as C
 import os
 import random
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HC = os.path.join(ROOT, "tests", "hostcheck")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
 class _Libs:
@@ -34,6 +36,7 @@ def hc():
     csrc = os.path.join(ROOT, "pcd_amd", "csrc")
     hdrs = [os.path.join(csrc, f) for f in ("fp.hip.h", "ec.hip.h", "pairing.hip.h", "pairing_vm.hip.h", "pairing_vm_gen.h", "vm_tables.h",
                                             "params_gen.h", "params28_gen.h")]
+    hdrs.append(os.path.join(ROOT, "tests", "gpucheck", "fieldops_ops.h"))   # the per-element code of hc_field_case_ops and its kin
     # HOSTCHECK_SAN=1 (tools/san/test_sanitizers.py, opt-in leg): load the harness the sanitizer recipes of tools/san built into build/san
     # (this file only picks the directory; every compiler flag of that build lives in tools/san/Makefile, which does not ship to the GPU box)
     if os.environ.get("HOSTCHECK_SAN") == "1":
@@ -79,27 +82,10 @@ def test_field_ops_and_abi_conversion(hc, fid):
 def test_add_sub_on_every_representative(hc, fid):
     """Fp::operator+ / operator- decide from the two top limbs whether 2p comes off / goes on and fall back to an exact carry chain
     when those cannot tell: operands are raw device images (any representative in [0, 2p)), aimed at the undecidable band."""
-    from oracle import pyoracle as O
-    f = O.FIELDS[fid]
-    p, N, B = f.p, (11 if fid < 2 else 27), 1 << 28
-    rnd = random.Random(77 + fid)
-    lo = B ** (N - 2)                      # weight of the second limb from the top
-    pairs = []
-    def both(a, b):
-        if 0 <= a < 2 * p and 0 <= b < 2 * p:
-            pairs.append((a, b))
-    for _ in range(2000):
-        both(rnd.randrange(2 * p), rnd.randrange(2 * p))
-    for a in [0, 1, p - 1, p, p + 1, 2 * p - 1] + [rnd.randrange(2 * p) for _ in range(40)]:
-        for d in (-2 * lo, -lo - 1, -lo, -lo + 1, -3, -2, -1, 0, 1, 2, 3, lo - 1, lo, lo + 1, 2 * lo):
-            both(a, 2 * p - a + d)         # sums around 2p: the band the estimate leaves open
-            both(a, a + d)                 # differences around 0
-            both(a + d, a)
-        both(a, a); both(a, 0); both(0, a); both(a, 2 * p - 1); both(2 * p - 1, a)
-    for _ in range(300):                   # differences whose two top limbs cancel
-        a = rnd.randrange(2 * p)
-        both(a, a - (a % lo) + rnd.randrange(lo))
-        both(a, (2 * p - a) - ((2 * p - a) % lo) + rnd.randrange(lo))
+    import field_reference as fr
+    f = fr.FLD[fid]
+    p, N, B = f.p, f.N, 1 << 28
+    pairs = fr.addsub_band_pairs(fid)      # (the generator lives in tests/field_reference.py: the device test runs the same pairs)
     def limbs(x):
         return [(x >> (28 * i)) & (B - 1) for i in range(N - 1)] + [x >> (28 * (N - 1))]
     A = np.array([limbs(a) for a, _ in pairs], dtype=np.uint32)
