@@ -100,6 +100,20 @@ int pcdhip_msm(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const 
 /* Same with scalars already resident on the device (element `scalar_offset` onwards). */
 int pcdhip_msm_dev(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const pcdhip_buf* scalars,
                    size_t scalar_offset, size_t n, uint64_t* out_xyz_mont);
+/* Short MSMs without buckets (msm_short.hip.h): the same arguments, encodings and result as pcdhip_msm / pcdhip_msm_dev -- a Jacobian
+ * point X || Y || Z with Z = 0 for the identity, the same affine image (the Jacobian representative may differ) -- at a cost that scales
+ * with n: one mixed addition per set scalar bit over the handle's resident copies, then a chain of c * (windows per copy) doublings
+ * (the scalar's bits on a handle without copies).  n == 0 gives the identity without a launch; n > 1024 PCDHIP_E_SIZE_UNSUPPORTED;
+ * PCDHIP_E_ARG for offset + n beyond the vector, a wrong field, null pointers, an unreduced scalar and sharded bases.  Runs on the
+ * context's own stream with a workspace of its own: outstanding MSM tickets are unaffected. */
+int pcdhip_msm_short(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const uint64_t* scalars_canonical,
+                     size_t n, uint64_t* out_xyz_mont);
+int pcdhip_msm_short_dev(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const pcdhip_buf* scalars,
+                         size_t scalar_offset, size_t n, uint64_t* out_xyz_mont);
+/* Opt-in routing: with max_n > 0 the witness MSMs of pcdhip_kzg_open and the two MSMs of pcdhip_kzg_check take the short path when
+ * they cover at most max_n pairs (at most 1024).  Default 0: never -- those functions then run exactly the code they ran before.
+ * Vectors uploaded through a multi-device context are sharded and keep the bucket pipeline. */
+int pcdhip_msm_set_short(pcdhip_ctx* ctx, size_t max_n);
 /* Throughput form of pcdhip_msm_dev for a caller with several INDEPENDENT MSMs to make (the commitments of a Marlin round over one
  * resident committer key, BASELINE configs[3]; consecutive steps of a benchmark): submit enqueues the MSM on one of the context's four
  * side streams (own stream and workspace, round robin) and returns at once with a ticket; collect waits for that submission and

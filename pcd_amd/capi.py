@@ -63,6 +63,7 @@ EXPORTS = [
     "pcdhip_multi_pairing", "pcdhip_pairing_set_mode", "pcdhip_groth16_verify", "pcdhip_groth16_verify_batch", "pcdhip_timer_start", "pcdhip_timer_stop",
     "pcdhip_poly_eval", "pcdhip_poly_lincomb", "pcdhip_poly_div_linear", "pcdhip_kzg_open", "pcdhip_kzg_check",
     "pcdhip_vec_mul", "pcdhip_vec_batch_inverse", "pcdhip_poly_div_vanishing", "pcdhip_poly_mul",
+    "pcdhip_msm_short", "pcdhip_msm_short_dev", "pcdhip_msm_set_short",
 ]
 
 
@@ -169,6 +170,23 @@ class Context:
             n = scalars.shape[0] if n is None else n
             self._check(lib().pcdhip_msm(self._ctx, bases._h, C.c_size_t(offset), _p(scalars), C.c_size_t(n), _p(out)))
         return out
+
+    def msm_short(self, bases, scalars, offset=0, n=None, scalar_offset=0):
+        """msm() for a few pairs (at most 1024) without buckets: bit-plane sums over the handle's resident copies.  `scalars`: canonical
+        limbs (numpy) or a DeviceBuf, then from element `scalar_offset` on.  Same result up to the Jacobian representative."""
+        out = np.zeros(3 * point_limbs(bases.curve, bases.group) // 2, dtype=np.uint64)
+        if isinstance(scalars, DeviceBuf):
+            n = scalars.n - scalar_offset if n is None else n
+            self._check(lib().pcdhip_msm_short_dev(self._ctx, bases._h, C.c_size_t(offset), scalars._h, C.c_size_t(scalar_offset), C.c_size_t(n), _p(out)))
+        else:
+            scalars = _u64(scalars)
+            n = scalars.shape[0] if n is None else n
+            self._check(lib().pcdhip_msm_short(self._ctx, bases._h, C.c_size_t(offset), _p(scalars), C.c_size_t(n), _p(out)))
+        return out
+
+    def msm_set_short(self, max_n):
+        """kzg_open / kzg_check run their MSMs over at most `max_n` pairs through msm_short (0, the default: never)."""
+        self._check(lib().pcdhip_msm_set_short(self._ctx, C.c_size_t(int(max_n))))
 
     def msm_submit(self, bases, scalars, offset=0, n=None, scalar_offset=0):
         """enqueue an MSM over resident scalars on a side stream -> ticket (at most four outstanding); see msm_collect"""

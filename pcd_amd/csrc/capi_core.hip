@@ -163,6 +163,7 @@ void pcdhip_destroy(pcdhip_ctx* ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   ctx->msm_ws.release();
   ctx->aux_ws.release();
+  ctx->short_ws.release();
   for (int k = 0; k < 6; k++) {
     ctx->g16_ws[k].release();
     if (ctx->g16_streams[k]) (void)hipStreamDestroy(ctx->g16_streams[k]);

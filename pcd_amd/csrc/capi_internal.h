@@ -73,6 +73,10 @@ int drop_side_streams(pcdhip_ctx* ctx, bool partial);
 bool pipe_pending(const pcdhip_ctx* ctx);
 void drain_peers(pcdhip_ctx* ctx);
 
+// ---- capi_msm_short.hip (the caller has bound the device; PCDHIP_E_ARG for a sharded handle or a range beyond the vector)
+int msm_short_common(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const uint32_t* scalars_dev, size_t n, uint64_t* out_xyz);
+int msm_short_host(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const uint64_t* scalars, size_t n, uint64_t* out_xyz);
+
 // ---- capi_fft.hip
 int pick_domain(int field_id, size_t min_size, Dom* d);
 int get_tables(pcdhip_ctx* ctx, int field_id, int log_n, const FftTables** out);

@@ -55,6 +55,7 @@ int kzg_witness(pcdhip_ctx* ctx, const pcdhip_bases* bases, const uint32_t* q_de
     memset(out_xyz, 0, (size_t)pcdhip_point_limbs(bases->curve_id, bases->group_id) / 2 * 3 * 8);
     return PCDHIP_OK;
   }
+  if (n <= ctx->msm_short_max) return msm_short_common(ctx, bases, 0, q_dev, n, out_xyz);  // pcdhip_msm_set_short: no buckets for a few pairs
   return msm_common(ctx, bases, 0, q_dev, n, out_xyz);
 }
 void mont_to_canonical(int fr, const uint64_t* in, uint64_t* out) {
@@ -211,8 +212,11 @@ int pcdhip_kzg_check(pcdhip_ctx* ctx, int curve_id, const uint64_t* g_xy, const 
   ctx->precompute = saved;
   if (rc) return rc;
   std::vector<uint64_t> jac(2 * j1);
-  rc = pcdhip_msm(ctx, b, 0, sc.data(), nb, jac.data());
-  rc = rc ? rc : pcdhip_msm(ctx, b, n, r.data(), n, &jac[j1]);
+  // (pcdhip_msm_set_short: each of the two MSMs skips the buckets when it covers few enough pairs; a multi-device context's vector is
+  //  sharded and keeps the bucket pipeline, which sums over the devices)
+  const bool may_short = b->shards.empty();
+  rc = may_short && nb <= ctx->msm_short_max ? msm_short_host(ctx, b, 0, sc.data(), nb, jac.data()) : pcdhip_msm(ctx, b, 0, sc.data(), nb, jac.data());
+  if (!rc) rc = may_short && n <= ctx->msm_short_max ? msm_short_host(ctx, b, n, r.data(), n, &jac[j1]) : pcdhip_msm(ctx, b, n, r.data(), n, &jac[j1]);
   pcdhip_bases_free(ctx, b);
   if (rc) return rc;
   std::vector<uint64_t> aff(2 * l1);

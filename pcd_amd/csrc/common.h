@@ -87,6 +87,8 @@ struct pcdhip_ctx {
   hipStream_t stream;
   pcd::MsmWorkspace msm_ws;
   pcd::MsmWorkspace aux_ws;  // fft ping-pong, witness-map vectors, groth16 scratch
+  pcd::MsmWorkspace short_ws;  // pcdhip_msm_short: scalars, plane partials, result (slots SHORT_*, capi_msm_short.hip)
+  size_t msm_short_max = 0;    // pcdhip_msm_set_short: the MSMs of pcdhip_kzg_open / _check over at most this many pairs skip the buckets (0: never)
   // the MSMs of a Groth16 proof run concurrently, each on its own stream with its own workspace: the
   // latency-bound bucket-reduction tail of one overlaps the throughput-bound accumulation of the others.
   // Streams 0 and 1 are created with the highest priority, 2 with the default one, 3..5 with the lowest.
@@ -179,6 +181,12 @@ struct GroupEntry {
   hipError_t (*fb_tables)(hipStream_t, const uint32_t* bases_abi, uint32_t ni, uint32_t* tables);
   hipError_t (*fb_inputs)(hipStream_t, const uint32_t* tables, const uint32_t* base0_abi, uint32_t ni, const uint32_t* scalars, uint32_t k,
                           uint32_t* scratch, uint32_t* out_abi, uint8_t* out_inf, uint32_t* out_z_abi, uint32_t out_stride);
+  // short MSM without buckets (msm_short.hip.h): bit-plane sums over the resident copies, 1 <= n <= MSM_SHORT_MAX_N.  scratch:
+  // msm_short_scratch_words(bases, n) u32 words, whose first word is the error word afterwards (a scalar was not reduced); out_dev: one
+  // Jacobian point in the device image
+  size_t (*msm_short_scratch_words)(const MsmBasesView& bases, uint32_t n);
+  hipError_t (*msm_short)(hipStream_t, const MsmBasesView& bases, const uint32_t* scalars, uint32_t n, uint32_t* scratch, uint32_t* out_dev);
+  void (*identity_abi)(uint32_t* out_abi);  // the identity (0 : 1 : 0) as a Jacobian point in the C-ABI image (host)
 };
 const GroupEntry& group_entry(int curve_id, int group_id);  // group_id 1 / 2
 

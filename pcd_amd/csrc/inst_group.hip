@@ -2,6 +2,7 @@
 // MSM driver + small point utilities instantiated for that group.
 #include "common.h"
 #include "fixed_base.hip.h"
+#include "msm_short.hip.h"
 
 namespace pcd {
 
@@ -85,6 +86,11 @@ hipError_t msm_entry(MsmWorkspace& ws, hipStream_t st, const MsmBasesView& bases
                      uint32_t* out_dev, int c, uint32_t chunk, int sort_mode, MsmTimings* tm, MsmSharedSort* share, int share_role) {
   return msm_run<GT>(ws, st, bases, scalars, n, out_dev, c, chunk, sort_mode, tm, share, share_role);
 }
+size_t msm_short_scratch_words_entry(const MsmBasesView& bases, uint32_t n) { return msm_short_plan<GT>(bases, n).scratch_words; }
+hipError_t msm_short_entry(hipStream_t st, const MsmBasesView& bases, const uint32_t* scalars, uint32_t n, uint32_t* scratch, uint32_t* out_dev) {
+  return msm_short_run<GT>(st, bases, scalars, n, scratch, out_dev);
+}
+void identity_abi_entry(uint32_t* out_abi) { Jac<F>::infinity().to_abi(out_abi); }
 hipError_t precompute_entry(hipStream_t st, uint32_t* pts, uint32_t n, int groups, int shift) {
   return msm_precompute<GT>(st, pts, n, groups, shift);
 }
@@ -131,7 +137,7 @@ hipError_t fb_inputs_entry(hipStream_t st, const uint32_t* tables, const uint32_
 const GroupEntry* PCD_CAT(pcd_group_entry_, PCD_GROUP_IDX)() {
   static const GroupEntry e = {Aff<F>::WORDS, MsmBaseStride<GT>::value, Aff<F>::ABI_WORDS, GT::FR::N32, GT::FR::BITS, msm_entry, precompute_entry,
                                points_in_entry, jac_out_entry, points_sum_entry, jac_sum_parts_entry, to_affine_entry, FB_TABLE_WORDS, fixed_base_entry,
-                               fb_tables_entry, fb_inputs_entry};
+                               fb_tables_entry, fb_inputs_entry, msm_short_scratch_words_entry, msm_short_entry, identity_abi_entry};
   return &e;
 }
 

@@ -40,6 +40,11 @@ extern "C" {
     pub fn pcdhip_set_precompute_budget(ctx: *mut pcdhip_ctx, bytes: usize) -> c_int;
     pub fn pcdhip_get_precompute_budget(ctx: *mut pcdhip_ctx, bytes: *mut usize) -> c_int;
     pub fn pcdhip_msm(ctx: *mut pcdhip_ctx, bases: *const pcdhip_bases, offset: usize, scalars: *const u64, n: usize, out_xyz: *mut u64) -> c_int;
+    // the same over short slices (at most 1024 pairs): no buckets, bit-plane sums over the handle's resident copies
+    pub fn pcdhip_msm_short(ctx: *mut pcdhip_ctx, bases: *const pcdhip_bases, offset: usize, scalars: *const u64, n: usize, out_xyz: *mut u64) -> c_int;
+    pub fn pcdhip_msm_short_dev(ctx: *mut pcdhip_ctx, bases: *const pcdhip_bases, offset: usize, scalars: *const pcdhip_buf, scalar_offset: usize, n: usize,
+                                out_xyz: *mut u64) -> c_int;
+    pub fn pcdhip_msm_set_short(ctx: *mut pcdhip_ctx, max_n: usize) -> c_int;
     pub fn pcdhip_to_affine(ctx: *mut pcdhip_ctx, curve: c_int, group: c_int, xyz: *const u64, n: usize, out_xy: *mut u64, out_inf: *mut u8) -> c_int;
     // K2: Radix2EvaluationDomain / GeneralEvaluationDomain transforms
     pub fn pcdhip_fft(ctx: *mut pcdhip_ctx, field: c_int, data: *mut u64, log_n: u32, inverse: c_int, coset: c_int) -> c_int;
