@@ -12,8 +12,9 @@
 //   2. msm_accumulate fixed-size chunks of the sorted list, one lane (or 2 / 3 lanes: lane-split extension fields) per chunk:
 //                    every lane does the same number of mixed additions whatever the scalar distribution; runs that cross
 //                    a chunk edge are emitted as "pieces"; lazily reduced XYZZ accumulator for the 298-bit G1 (int-VALU-bound)
-//   3. msm_fixup / msm_big_segments / msm_big_bucket   pieces of one bucket are summed; flushed records become Jacobian points
-//   4. msm_tail_level / msm_tail_pair  sum_d d*B_d by blocked running sums, then pair levels (two lanes per group operation)
+//   3. msm_fixup / msm_big_segments / msm_big_bucket   one item per chunk edge: the pieces of a bucket that crosses edges are summed
+//   4. msm_tail_level / msm_tail_pair  sum_d d*B_d by blocked running sums, then pair levels (two lanes per group operation); the first
+//                    level takes every bucket from where it lies (msm_bucket_at: flushed records become Jacobian points as they are read)
 //   5. msm_horner    windows combined by c doublings each (not needed with one precomputed copy of the bases per window)
 //
 // Zero digits never enter the sorted list (upstream skips zero scalars); scalars equal to one go, staged per workgroup, to a list
@@ -409,17 +410,43 @@ static __global__ void __launch_bounds__(1024) scan_apply(const uint32_t* __rest
 // them) and the points at infinity of a key (28 .. 41 % of a real a / b query), and a grid planned for n W entries then runs a last round
 // that is nearly empty (A of the bench's proof: 2.07 rounds of work took three) or, for a short list, gives a quarter of the lanes 40
 // entries each while the others idle (2^16 pairs: 10 entries per lane on average).  `lanes` = chunks the device runs at a time; the list
-// is spread over whole rounds of them, `lo` <= chunk <= `hi` (lanes < 2^20, lo and hi < 64).
-PCD_HD uint32_t msm_plan_chunk(uint32_t M, uint32_t lanes, uint32_t lo, uint32_t hi) {
+// is spread over whole rounds of them, `lo` <= chunk <= `hi` (lanes < 2^20, lo and hi < 256): the fewest rounds of `hi`-entry
+// chunks that hold the list, then the shortest chunk that still holds it in that many rounds.  A larger `hi` therefore only changes
+// lists longer than one round of the smaller one (57 entries per lane: one round of 57 under hi = 128, two of 29 under 56); a list
+// of at most lanes x lo entries gets `lo` whatever `hi` is.
+PCD_HD uint64_t msm_plan_rounds(uint32_t M, uint32_t lanes, uint32_t hi) {
   const uint64_t per_round = (uint64_t)lanes * hi;
-  const uint64_t rounds = ((uint64_t)M + per_round - 1) / per_round;
+  return ((uint64_t)M + per_round - 1) / per_round;
+}
+PCD_HD uint32_t msm_plan_chunk(uint32_t M, uint32_t lanes, uint32_t lo, uint32_t hi) {
+  const uint64_t rounds = msm_plan_rounds(M, lanes, hi);
   const uint32_t chunk = rounds ? (uint32_t)(((uint64_t)M + (uint64_t)lanes * rounds - 1) / ((uint64_t)lanes * rounds)) : lo;
   return chunk < lo ? lo : chunk > hi ? hi : chunk;
 }
-// (every lane of the accumulate and fix-up kernels evaluates this itself from the plan word `lanes | lo << 20 | hi << 26`: two divisions
-//  against a launch on the critical path of every MSM)
-PCD_HD uint32_t msm_plan_word(uint32_t lanes, uint32_t lo, uint32_t hi) { return lanes | (lo << 20) | (hi << 26); }
-PCD_HD uint32_t msm_chunk_of_plan(uint32_t M, uint32_t plan) { return msm_plan_chunk(M, plan & 0xFFFFFu, (plan >> 20) & 63u, (plan >> 26) & 63u); }
+// (every lane of the accumulate and edge kernels and of the first reduction level evaluates this itself from the 64-bit plan word
+//  `lanes | lo << 20 | hi << 28`: two divisions against a launch on the critical path of every MSM)
+constexpr uint32_t MSM_CHUNK_MAX = 128;  // longest chunk the device may choose (PCDHIP_CHUNK_HI's upper end)
+// Default upper bound of the device's choice.  128 gives the headline list (15 x 2^20 entries, 131 072 lanes) ONE round of 120-entry
+// chunks instead of three of 40 -- a third of the chunk edges, a shorter fix-up -- but the accumulation kernel itself measured slower
+// with it on the same box and the step the same within its spread ("Epilogue A/B"; records: profiles/ab_epilogue_*):
+// left at 56.  PCDHIP_CHUNK_HI = 16 .. 128 is the A/B knob.
+#ifndef PCD_CHUNK_HI
+#define PCD_CHUNK_HI 56
+#endif
+constexpr uint32_t MSM_CHUNK_HI = PCD_CHUNK_HI;
+PCD_HD uint64_t msm_plan_word(uint32_t lanes, uint32_t lo, uint32_t hi) { return (uint64_t)lanes | ((uint64_t)lo << 20) | ((uint64_t)hi << 28); }
+PCD_HD uint32_t msm_chunk_of_plan(uint32_t M, uint64_t plan) {
+  return msm_plan_chunk(M, (uint32_t)(plan & 0xFFFFFu), (uint32_t)(plan >> 20) & 255u, (uint32_t)(plan >> 28) & 255u);
+}
+// how the kernels behind the accumulation learn the chunk it ran with: the pair tree's device word, the plan word, or the value as given
+struct MsmChunkRule {
+  const uint32_t* chunk_dev;
+  uint64_t plan;
+  uint32_t chunk;
+  PCD_DEV uint32_t eval(const uint32_t* __restrict__ off, uint32_t nkeys) const {
+    return chunk_dev ? *chunk_dev : plan ? msm_chunk_of_plan(off[nkeys], plan) : chunk;
+  }
+};
 
 // key of sorted position p: largest key with off[key] <= p (skipping empty buckets)
 PCD_DEV uint32_t msm_find_key(const uint32_t* __restrict__ off, uint32_t nkeys, uint32_t p) {
@@ -514,7 +541,7 @@ struct MsmRunPlain<G, false> {
 // The lazily reduced accumulator is flushed AS IT IS (XYZZ: X carry-propagated < 16p, Y / ZZ / ZZZ reduced; the identity as
 // ZZ = 0) into records of four field elements: the products that turn it into a reduced Jacobian point would run inside the divergent
 // flush branch that some lane of the wave takes in nearly every iteration.  Whatever msm_accumulate wrote -- buckets and pieces -- is
-// converted by its reader (MsmStored::load: the fix-up pass, one lane per bucket, coalesced and convergent).
+// converted by its reader (MsmStored::load: the edge pass for pieces, the first reduction level for whole buckets).
 template <class G>
 struct MsmRunLazy {
   typedef typename G::F F;
@@ -594,7 +621,7 @@ struct MsmStoredPlain {  // XYZZ record
     typename EC<G>::AccX a = {F::load(p), F::load(p + F::WORDS), F::load(p + 2 * F::WORDS), F::load(p + 3 * F::WORDS)};
     return EC<G>::x_to_jac(a);
   }
-  static constexpr bool SEPARATE = true;  // flushed buckets live in their own array (four coordinates); the fix-up pass fills the bucket array
+  static constexpr bool SEPARATE = true;  // flushed buckets live in their own array (four coordinates); the Jacobian array holds what the edge pass summed
 };
 template <class G>
 struct MsmStoredPlain<G, false> {  // Jacobian record
@@ -620,7 +647,7 @@ struct MsmStored<G, true> {
     a.ZZZ = F::load(p + 3 * F::WORDS);
     return EC<G>::lz_to_jac(a);
   }
-  static constexpr bool SEPARATE = true;  // flushed buckets live in their own array (wider records); the fix-up pass fills the bucket array
+  static constexpr bool SEPARATE = true;  // flushed buckets live in their own array (wider records); the Jacobian array holds what the edge pass summed
 };
 
 // Waves per SIMD the register allocation of the accumulate kernel aims at: 2 for the 298-bit G1 (194 registers, no spills);
@@ -651,7 +678,7 @@ __global__ void __launch_bounds__(64, MsmAccWaves<G>::value) msm_accumulate_kern
                                                             const uint32_t* __restrict__ off, uint32_t nkeys,
                                                             uint32_t chunk, uint32_t* __restrict__ buckets,
                                                             uint32_t* __restrict__ piece_first, uint32_t* __restrict__ piece_last,
-                                                            uint32_t plan /* msm_plan_word, or 0: `chunk` as given */) {
+                                                            uint64_t plan /* msm_plan_word, or 0: `chunk` as given */) {
   if (plan) chunk = msm_chunk_of_plan(off[nkeys], plan);
   // GA: the configuration the arithmetic runs in -- G itself, or its lane-split form (Fq2 over lane pairs, Fq3 over lane triples:
   // the lanes of a group share one chunk, each holding one coefficient of every coordinate; memory images are the same)
@@ -1068,39 +1095,43 @@ __global__ void __launch_bounds__(64) msm_merge_ones_kernel(uint32_t* __restrict
   EC<GA>::add(a, b).store(buckets + (size_t)1 * Jac<F>::WORDS);
 }
 
-// One lane per bucket: a bucket whose sorted run crosses chunk edges is the sum of the pieces its chunks
-// emitted (piece_last of the first and middle chunks, piece_first of the last one).  Buckets with more than
-// `big_limit` pieces (e.g. "scalar = 1" of a bit-heavy witness, or the low buckets that the short top window
-// fills) go to the big list and are summed by one wave each.
+// One item per chunk edge: a bucket whose sorted run crosses chunk edges is the sum of the pieces its chunks emitted (piece_last of the
+// first and middle chunks, piece_first of the last one).  Item 2 + t looks at the run that is open at the end of chunk t, and only the
+// chunk that holds the run's FIRST piece sums it, into the Jacobian bucket array.  Buckets with more than `big_limit` pieces (e.g.
+// "scalar = 1" of a bit-heavy witness, or the low buckets that the short top window fills) go to the big list and are summed by one wave
+// each.  Whole buckets -- their run inside one chunk -- stay where msm_accumulate flushed them and empty ones are written by nobody:
+// the first reduction level takes every bucket from where it lies (msm_bucket_at).  The two buckets msm_merge_ones_kernel works on in
+// place, (window 0, digit 1) and the pseudo bucket, are always materialised in the Jacobian array: items 0 and 1.
 template <class G>
-__global__ void __launch_bounds__(64) msm_fixup_kernel(const uint32_t* __restrict__ off, uint32_t nkeys, uint32_t chunk,
+__global__ void __launch_bounds__(64) msm_fixup_kernel(const uint32_t* __restrict__ off, uint32_t nkeys, const MsmChunkRule rule,
                                                        const uint32_t* __restrict__ piece_first, const uint32_t* __restrict__ piece_last,
                                                        const uint32_t* __restrict__ acc_buckets /* what msm_accumulate flushed whole buckets into */,
                                                        uint32_t* __restrict__ buckets, uint32_t big_limit, uint32_t* __restrict__ big_count,
                                                        uint32_t* __restrict__ big_list /* (key, first segment, #segments) */, uint32_t big_cap,
-                                                       uint32_t* __restrict__ seg_list /* (t_lo, t_hi, t_last) */, uint32_t seg_len,
-                                                       const uint32_t* __restrict__ chunk_dev /* the pair tree's chunk, decided on the device */,
-                                                       uint32_t plan /* msm_plan_word of the running-sum form, or 0 */) {
-  if (chunk_dev) chunk = *chunk_dev;
-  else if (plan) chunk = msm_chunk_of_plan(off[nkeys], plan);
+                                                       uint32_t* __restrict__ seg_list /* (t_lo, t_hi, t_last) */, uint32_t seg_len) {
+  const uint32_t chunk = rule.eval(off, nkeys);
   typedef typename MsmItems<G>::GA GA;
   typedef typename GA::F F;
   typedef EC<GA> E;
   constexpr int RW = MsmStored<GA>::WORDS;
   if (MsmItems<G>::idle()) return;
   const bool lead = threadIdx.x % MsmItems<G>::LANES == 0;  // one lane of the item does the list bookkeeping
-  uint32_t key = MsmItems<G>::item();
-  if (key >= nkeys) return;
-  uint32_t lo = off[key], hi = off[key + 1];
-  if (hi == lo) {  // empty bucket: nobody else writes it, and the identity is Z = 0 (X, Y are never looked at then)
-    F::zero().store(buckets + (size_t)key * Jac<F>::WORDS + 2 * F::WORDS);
+  const uint32_t item = MsmItems<G>::item();
+  if (item < 2) {  // bucket (window 0, digit 1) and the pseudo bucket (key nkeys - 1), unless an edge item sums them
+    const uint32_t key = item == 0 ? 1u : nkeys - 1;
+    const uint32_t lo = off[key], hi = off[key + 1];
+    if (hi == lo) F::zero().store(buckets + (size_t)key * Jac<F>::WORDS + 2 * F::WORDS);  // the identity is Z = 0 (X, Y are never looked at then)
+    else if (MsmStored<GA>::SEPARATE && hi - (lo / chunk) * chunk <= chunk)  // the run ends inside the chunk it starts in
+      MsmStored<GA>::load(acc_buckets + (size_t)key * RW).store(buckets + (size_t)key * Jac<F>::WORDS);
     return;
   }
-  uint32_t t0 = lo / chunk, t1 = (hi - 1) / chunk;
-  if (t1 == t0) {  // the whole run lies inside one chunk: msm_accumulate wrote the bucket itself (unreduced for the lazy groups)
-    if (MsmStored<GA>::SEPARATE) MsmStored<GA>::load(acc_buckets + (size_t)key * RW).store(buckets + (size_t)key * Jac<F>::WORDS);
-    return;
-  }
+  const uint32_t t0 = item - 2;
+  const uint64_t edge = ((uint64_t)t0 + 1) * chunk;  // first list position of chunk t0 + 1
+  if (edge >= off[nkeys]) return;                    // the list ends in chunk t0 or before it
+  const uint32_t key = msm_find_key(off, nkeys, (uint32_t)edge - 1);
+  const uint32_t lo = off[key], hi = off[key + 1];
+  if (hi <= (uint32_t)edge || lo / chunk != t0) return;  // no run open at this edge, or its first piece lies in an earlier chunk
+  const uint32_t t1 = (hi - 1) / chunk;                  // (> t0: position `edge` belongs to the run)
   if (t1 - t0 + 1 > big_limit) {  // big bucket: its pieces are cut into segments of seg_len, one wave each
     if (!lead) return;
     uint32_t nseg = (t1 - t0 + seg_len) / seg_len;
@@ -1223,8 +1254,30 @@ __global__ void __launch_bounds__(64) msm_big_bucket_kernel(const uint32_t* __re
 //   V = S(C) + S(L) + WS({K * T_j}_{j>=1});   A' = {2^k T_j}_{j>=1},  C' = blocksums(C) ++ L
 // (WIDE: two lanes per item where the group allows it -- pays when the level is latency-bound, i.e. has few items; a first level over
 //  2^16 blocks fills the chip with one lane per item: G1-298 at c = 20 measured 0.71 -> 0.73 ms with two, G1-753 at c = 19 2.79 -> 2.32)
+// The FIRST level reads the buckets from where the accumulation and the edge pass left them: nothing copies whole buckets into the
+// Jacobian array or writes identities for empty ones.
+struct MsmBucketSrc {
+  const uint32_t* off;          // run of bucket `key`: [off[key], off[key + 1])
+  const uint32_t* acc_buckets;  // flushed records of whole buckets (MsmStored; the Jacobian array itself where the flush is Jacobian)
+  const uint32_t* buckets;      // Jacobian array: buckets summed by the edge pass or the big-bucket kernels, and bucket 1
+  uint32_t nkeys;
+  MsmChunkRule rule;
+};
+template <class GA>
+PCD_DEV Jac<typename GA::F> msm_bucket_at(const MsmBucketSrc& bs, uint32_t chunk, uint32_t key) {
+  typedef typename GA::F F;
+  if (key != 1) {  // (bucket 1 is always materialised: msm_merge_ones_kernel adds the pseudo bucket to it in place)
+    const uint32_t lo = bs.off[key], hi = bs.off[key + 1];
+    if (hi == lo) return Jac<F>::infinity();
+    if (hi - (lo / chunk) * chunk <= chunk)  // the run ends inside the chunk it starts in (one division)
+      return MsmStored<GA>::load(bs.acc_buckets + (size_t)key * MsmStored<GA>::WORDS);
+  }
+  return Jac<F>::load(bs.buckets + (size_t)key * Jac<F>::WORDS);
+}
+// (msm_tail_level_kernel is only ever the first level -- blocks of 8 over a large bucket array: A is the bucket array, window w's digit
+//  d at key w * strideA_in + d, and there is no C yet)
 template <class G, bool WIDE>
-__global__ void __launch_bounds__(64) msm_tail_level_kernel(const uint32_t* __restrict__ A_in, uint32_t mA, size_t strideA_in,
+__global__ void __launch_bounds__(64) msm_tail_level_kernel(const MsmBucketSrc bs, uint32_t mA, size_t strideA_in,
                                                             const uint32_t* __restrict__ C_in, uint32_t mC, size_t strideC_in,
                                                             uint32_t* __restrict__ A_out, size_t strideA_out,
                                                             uint32_t* __restrict__ C_out, size_t strideC_out, int k) {
@@ -1239,11 +1292,12 @@ __global__ void __launch_bounds__(64) msm_tail_level_kernel(const uint32_t* __re
   uint32_t tid = IT::item();
   uint32_t w = blockIdx.y;
   if (tid < JA) {
-    const uint32_t* A = A_in + w * strideA_in * PW;
+    const uint32_t chunk = bs.rule.eval(bs.off, bs.nkeys);
+    const uint32_t key1 = w * (uint32_t)strideA_in + 1;  // digit 1 of window w
     Jac<F> run = Jac<F>::infinity(), acc = Jac<F>::infinity();
     for (int tt = (int)K - 1; tt >= 0; tt--) {
       uint32_t i = tid * K + tt;
-      if (i < mA) run = O::add(run, Jac<F>::load(A + (size_t)i * PW));
+      if (i < mA) run = O::add(run, msm_bucket_at<GA>(bs, chunk, key1 + i));
       acc = O::add(acc, run);
     }
     if (IT::writer()) acc.store(C_out + (w * strideC_out + JC + tid) * PW);
@@ -1269,9 +1323,11 @@ __global__ void __launch_bounds__(64) msm_tail_level_kernel(const uint32_t* __re
 //   z = 0:  A'_{j-1} = 2 (A_{2j} + A_{2j+1})        z = 1:  L_j = A_{2j} + 2 A_{2j+1} -> C'[JC + j]        z = 2:  C'_j = C_{2j} + C_{2j+1}
 // (items and operations: MsmPairItems / MsmPairOps above)
 // one piece of a pair level: role 0 / 1 / 2 for item j of window w (the lanes of the item call it together)
-template <class G, bool Q = true>
+// (`bs`: the first level of a small bucket array, whose A is the buckets where they lie -- msm_bucket_at; nullptr: A_in)
+template <class G, bool Q = true, bool FIRST = false>
 PCD_DEV void msm_tail_pair_item(int role, uint32_t j, uint32_t w, const uint32_t* A_in, uint32_t mA, size_t strideA_in, const uint32_t* C_in,
-                                uint32_t mC, size_t strideC_in, uint32_t* A_out, size_t strideA_out, uint32_t* C_out, size_t strideC_out) {
+                                uint32_t mC, size_t strideC_in, uint32_t* A_out, size_t strideA_out, uint32_t* C_out, size_t strideC_out,
+                                const MsmBucketSrc* bs = nullptr) {
   typedef MsmPairOps<G, MsmPairItems<G, true>::TWO, Q> O;
   typedef typename O::GA GA;
   typedef typename GA::F F;
@@ -1280,16 +1336,21 @@ PCD_DEV void msm_tail_pair_item(int role, uint32_t j, uint32_t w, const uint32_t
   const uint32_t JA = (mA + 1) >> 1, JC = (mC + 1) >> 1;
   if (role < 2) {
     if (j >= JA) return;
-    const uint32_t* A = A_in + w * strideA_in * PW;
+    uint32_t chunk = 0;
+    if constexpr (FIRST) chunk = bs->rule.eval(bs->off, bs->nkeys);
+    auto a_at = [&](uint32_t i) {
+      if constexpr (FIRST) return msm_bucket_at<GA>(*bs, chunk, w * (uint32_t)strideA_in + 1 + i);
+      else return Jac<F>::load(A_in + (w * strideA_in + i) * PW);
+    };
     const bool two = 2 * j + 1 < mA;
-    const Jac<F> a0 = Jac<F>::load(A + (size_t)(2 * j) * PW);
+    const Jac<F> a0 = a_at(2 * j);
     if (role == 0) {
       if (j == 0) return;
-      Jac<F> run = two ? O::add(a0, Jac<F>::load(A + (size_t)(2 * j + 1) * PW)) : a0;
+      Jac<F> run = two ? O::add(a0, a_at(2 * j + 1)) : a0;
       run = O::dbl(run);
       if (IT::writer()) run.store(A_out + (w * strideA_out + j - 1) * PW);
     } else {
-      Jac<F> acc = two ? O::add(O::dbl(Jac<F>::load(A + (size_t)(2 * j + 1) * PW)), a0) : a0;
+      Jac<F> acc = two ? O::add(O::dbl(a_at(2 * j + 1)), a0) : a0;
       if (IT::writer()) acc.store(C_out + (w * strideC_out + JC + j) * PW);
     }
   } else {
@@ -1308,6 +1369,15 @@ __global__ void __launch_bounds__(64) msm_tail_pair_kernel(const uint32_t* __res
   typedef MsmPairItems<G, true, Q> IT;
   if (IT::idle()) return;
   msm_tail_pair_item<G, Q>((int)blockIdx.z, IT::item(), blockIdx.y, A_in, mA, strideA_in, C_in, mC, strideC_in, A_out, strideA_out, C_out, strideC_out);
+}
+// the first level of a small bucket array (under 2^17 buckets a window): the same pair level over the buckets where they lie; no C yet
+template <class G, bool Q = true>
+__global__ void __launch_bounds__(64) msm_tail_pair_first_kernel(const MsmBucketSrc bs, uint32_t mA, size_t strideA_in,
+                                                                 uint32_t* __restrict__ A_out, size_t strideA_out,
+                                                                 uint32_t* __restrict__ C_out, size_t strideC_out) {
+  typedef MsmPairItems<G, true, Q> IT;
+  if (IT::idle()) return;
+  msm_tail_pair_item<G, Q, true>((int)blockIdx.z, IT::item(), blockIdx.y, nullptr, mA, strideA_in, nullptr, 0u, 0, A_out, strideA_out, C_out, strideC_out, &bs);
 }
 // The LAST pair levels in one launch: once a level's 2 JA + JC pieces fit the item slots of one workgroup of FOUR waves -- one wave per
 // SIMD of a CU: with eight, two waves share a SIMD and every level takes 1.6x as long, more than the launch it saves (measured: tail
@@ -1577,19 +1647,19 @@ hipError_t msm_run(MsmWorkspace& ws, hipStream_t st, const MsmBasesView& bv, con
   }
   const MsmLane* lane = ws.lane;
   const int plan_cus = lane && lane->cus > 0 ? lane->cus : cus;  // the accumulate grid fills whole rounds of the CUs its queue may use
-  // (round 5: the chunk is chosen on the device from the actual list length -- msm_plan_chunk -- between chunk_lo and 56; the host
-  //  sizes grids and piece arrays for chunk_lo, which is 40 as before for a list that is long even when sparse and goes down to 16 for one
-  //  that cannot fill four rounds of the lanes)
+  // (round 5: the chunk is chosen on the device from the actual list length -- msm_plan_chunk -- between chunk_lo and MSM_CHUNK_HI; the
+  //  host sizes grids and piece arrays for chunk_lo, which is 40 as before for a list that is long even when sparse and goes down to 16 for
+  //  one that cannot fill four rounds of the lanes)
   uint32_t acc_lanes = 0, chunk_lo = 0;
   static const uint32_t chunk_hi_env = getenv("PCDHIP_CHUNK_HI") ? (uint32_t)atoi(getenv("PCDHIP_CHUNK_HI")) : 0u;  // developer knob (A/B of the upper bound)
-  const uint32_t chunk_hi = chunk_hi_env >= 16 && chunk_hi_env <= 63 ? chunk_hi_env : 56;
+  const uint32_t chunk_hi = chunk_hi_env >= 16 && chunk_hi_env <= MSM_CHUNK_MAX ? chunk_hi_env : MSM_CHUNK_HI;
   if (!chunk_override && !use_tree) {
     acc_lanes = (uint32_t)plan_cus * 4 * MsmAccWaves<G>::value * (64 / AccOf<G>::LANES);
     chunk_lo = (uint32_t)std::min<uint64_t>(40, std::max<uint64_t>(16, (maxM + 4ull * acc_lanes - 1) / (4ull * acc_lanes)));
     pl.chunk = chunk_lo;
   }
-  const uint32_t plan_word = acc_lanes && acc_lanes < (1u << 20) && chunk_hi < 64 ? msm_plan_word(acc_lanes, chunk_lo, chunk_hi) : 0u;
-  if (acc_lanes && !plan_word) pl.chunk = 40;  // (a device or knob outside the plan word's ranges: the fixed chunk of rounds 1-4)
+  const uint64_t plan_word = acc_lanes && acc_lanes < (1u << 20) ? msm_plan_word(acc_lanes, chunk_lo, chunk_hi) : 0u;
+  if (acc_lanes && !plan_word) pl.chunk = 40;  // (a device outside the plan word's range: the fixed chunk of rounds 1-4)
   if (maxM >= 0xFFFFFFF0ull || (uint64_t)bv.n_total * bv.groups >= 0x7FFFFFF0ull) return hipErrorInvalidValue;  // bit 31 of an entry: sign
 
   EventSet<9> ev;
@@ -1740,8 +1810,8 @@ hipError_t msm_run(MsmWorkspace& ws, hipStream_t st, const MsmBasesView& bv, con
   uint32_t* big = (uint32_t*)ws.buf[WS_BIG];
   uint32_t* seg_list = big + 3 * big_cap;
   uint32_t* big_partial = (uint32_t*)ws.buf[WS_BIGPART];
-  // (no memset of the bucket array -- 69 MB at c = 19: every bucket is written by exactly one of msm_accumulate, msm_fixup
-  //  (also the empty ones: Z = 0) and msm_big_bucket)
+  // (no memset of the bucket arrays -- 69 MB at c = 19: a non-empty bucket is written by exactly one of msm_accumulate, msm_fixup and
+  //  msm_big_bucket, and the first reduction level never looks at an empty one: msm_bucket_at)
   PCD_HIP_TRY(mark(8));  // the accumulate stage time is the kernel alone (mark 8 -> mark 4)
   hipStream_t own = st;
   if (lane) {  // the accumulation runs on the lane, behind the other MSMs' accumulations queued there before it
@@ -1788,9 +1858,11 @@ hipError_t msm_run(MsmWorkspace& ws, hipStream_t st, const MsmBasesView& bv, con
     PCD_HIP_TRY(hipStreamWaitEvent(st, ws.lane_out, 0));
   }
   PCD_HIP_TRY(mark(4));
-  // 5. pieces
-  hipLaunchKernelGGL((msm_fixup_kernel<G>), dim3(MsmItems<G>::grid(tkeys)), dim3(64), 0, st, off, tkeys, pl.chunk, pfirst, plast, acc_buckets, buckets,
-                     big_limit, big_count, big, big_cap, seg_list, seg_len, tree_chunk_dev, plan_word);
+  // 5. pieces: one item per chunk edge (sized, like the piece arrays, for the shortest chunk the device may pick) + the two of bucket 1
+  //    and the pseudo bucket
+  const MsmChunkRule chunk_rule = {tree_chunk_dev, plan_word, pl.chunk};
+  hipLaunchKernelGGL((msm_fixup_kernel<G>), dim3(MsmItems<G>::grid(nchunks + 2)), dim3(64), 0, st, off, tkeys, chunk_rule, pfirst, plast, acc_buckets,
+                     buckets, big_limit, big_count, big, big_cap, seg_list, seg_len);
   {
     const uint32_t big_grid = std::min<uint32_t>(seg_cap, 2048);
     PCD_HIP_TRY(ws.ensure(WS_BIGSCR, (size_t)big_grid * 64 * PB));
@@ -1810,7 +1882,8 @@ hipError_t msm_run(MsmWorkspace& ws, hipStream_t st, const MsmBasesView& bv, con
     PCD_HIP_TRY(ws.ensure(WS_C0, (size_t)Wg * cap_pts * PB / 2 + PB * Wg * 4));
     PCD_HIP_TRY(ws.ensure(WS_C1, (size_t)Wg * cap_pts * PB / 2 + PB * Wg * 4));
     const size_t strideAC = cap_pts / 2 + 4;
-    const uint32_t* A_in = buckets + PW;  // bucket d = 1 of window 0
+    const MsmBucketSrc bucket_src = {off, acc_buckets, buckets, tkeys, chunk_rule};  // A of the first level: msm_bucket_at
+    const uint32_t* A_in = buckets + PW;  // (bucket d = 1 of window 0)
     size_t strideA_in = (size_t)1 << pl.c;
     const uint32_t* C_in = nullptr;
     size_t strideC_in = 0;
@@ -1834,18 +1907,24 @@ hipError_t msm_run(MsmWorkspace& ws, hipStream_t st, const MsmBasesView& bv, con
       }
       if (fused) {
         // (the host only follows the level sequence to know where the result ends up)
-      } else if (k == 1 && std::max(JA, JC) * (uint32_t)Wg > MSM_QUAD_MAX_ITEMS)   // a level this wide is throughput: two lanes per operation
+      } else if (level == 0 && k == 1 && JA * (uint32_t)Wg > MSM_QUAD_MAX_ITEMS)  // (the first level: the buckets from where they lie)
+        hipLaunchKernelGGL((msm_tail_pair_first_kernel<G, false>), dim3(MsmPairItems<G, true, false>::grid(JA), Wg, 2), dim3(64), 0, st, bucket_src, mA,
+                           strideA_in, A_out, strideAC, C_out, strideAC);
+      else if (level == 0 && k == 1)
+        hipLaunchKernelGGL((msm_tail_pair_first_kernel<G>), dim3(MsmPairItems<G>::grid(JA), Wg, 2), dim3(64), 0, st, bucket_src, mA, strideA_in, A_out,
+                           strideAC, C_out, strideAC);
+      else if (k == 1 && std::max(JA, JC) * (uint32_t)Wg > MSM_QUAD_MAX_ITEMS)   // a level this wide is throughput: two lanes per operation
         hipLaunchKernelGGL((msm_tail_pair_kernel<G, false>), dim3(MsmPairItems<G, true, false>::grid(std::max(JA, JC)), Wg, 3), dim3(64), 0, st, A_in, mA,
                            strideA_in, C_in, mC, strideC_in, A_out, strideAC, C_out, strideAC);
       else if (k == 1)
         hipLaunchKernelGGL((msm_tail_pair_kernel<G>), dim3(MsmPairItems<G>::grid(std::max(JA, JC)), Wg, 3), dim3(64), 0, st, A_in, mA, strideA_in, C_in,
                            mC, strideC_in, A_out, strideAC, C_out, strideAC);
       else if (threads <= (1u << 15))
-        hipLaunchKernelGGL((msm_tail_level_kernel<G, true>), dim3(MsmPairItems<G, true>::grid(threads), Wg), dim3(64), 0, st, A_in, mA, strideA_in, C_in, mC,
-                           strideC_in, A_out, strideAC, C_out, strideAC, k);
+        hipLaunchKernelGGL((msm_tail_level_kernel<G, true>), dim3(MsmPairItems<G, true>::grid(threads), Wg), dim3(64), 0, st, bucket_src, mA, strideA_in, C_in,
+                           mC, strideC_in, A_out, strideAC, C_out, strideAC, k);
       else
-        hipLaunchKernelGGL((msm_tail_level_kernel<G, false>), dim3(MsmPairItems<G, false>::grid(threads), Wg), dim3(64), 0, st, A_in, mA, strideA_in, C_in, mC,
-                           strideC_in, A_out, strideAC, C_out, strideAC, k);
+        hipLaunchKernelGGL((msm_tail_level_kernel<G, false>), dim3(MsmPairItems<G, false>::grid(threads), Wg), dim3(64), 0, st, bucket_src, mA, strideA_in, C_in,
+                           mC, strideC_in, A_out, strideAC, C_out, strideAC, k);
       mA = JA ? JA - 1 : 0;
       mC = JC + JA;
       A_in = A_out; strideA_in = strideAC;
