@@ -437,7 +437,7 @@ int pcdhip_vk_deserialize(int curve_id, const uint8_t* in, size_t in_len, int co
                           uint64_t* delta_g2, uint64_t* gamma_abc_g1, uint8_t* gamma_abc_inf, size_t max_inputs, size_t* num_inputs);
 
 /* ---- K7 open side: KZG10 / MarlinKZG10 openings ------------------------------------------------------------------------
- * The open half of ark-poly-commit's KZG10 (the commit half is the prefix MSM above over the resident powers).  Polynomials are
+ * The open half of ark-poly-commit's KZG10 (the commit half is pcdhip_kzg_commit below).  Polynomials are
  * device vectors of ABI Montgomery coefficients, low degree first (lens[j] of them, at most the buffer's n); field elements are in
  * ABI Montgomery form, MSM scalars stay canonical.  Every division / evaluation runs on the device in three stream-ordered launches
  * (tile values, one carry scan, the tiles again from their carries); only the pairing check's scalar bookkeeping is on the host. */
@@ -465,6 +465,42 @@ int pcdhip_kzg_check(pcdhip_ctx* ctx, int curve_id, const uint64_t* g_xy, const 
                      const uint64_t* beta_h_xy, size_t n, const uint64_t* comms_xy, const uint8_t* comms_inf, const uint64_t* points_mont,
                      const uint64_t* values_mont, const uint64_t* w_xy, const uint8_t* w_inf, const uint64_t* random_v_mont,
                      const uint64_t* randomizers_canonical, int* ok);
+
+/* ---- K7 commit side: KZG10 / MarlinKZG10 commitments of device-resident polynomials ------------------------------------
+ * Replaces ark-poly-commit `KZG10::commit` and the loop of `MarlinKZG10::commit` over the labeled polynomials of one AHP round
+ * (SURVEY.md A.7), for polynomials that already live on the device as ABI Montgomery coefficients (what pcdhip_fft_dev, pcdhip_poly_mul,
+ * pcdhip_poly_div_vanishing, pcdhip_poly_lincomb and pcdhip_vec_* leave): one launch turns all of them into the canonical scalars the MSMs
+ * take and finds their trimmed lengths, up to four items' MSMs run side by side on the streams of pcdhip_msm_submit, the hiding MSMs
+ * beside them, and one epilogue adds, normalises and copies back.  No coefficient crosses PCIe.  The library draws no randomness: the
+ * blinding polynomials (`Randomness::blinding_polynomial`, and `shifted_rand` of a degree-bound commitment) are inputs.
+ *   comm[j]    = MSM(powers_of_g[0 .. t_j), p_j) + MSM(powers_of_gamma_g[0 .. blinding_len), blinding_j)
+ *   shifted[j] = MSM(shifted_powers_of_g[shifted_offset .. shifted_offset + t_j), p_j)
+ *                + MSM(powers_of_gamma_g[0 .. shifted_blinding_len), shifted_blinding_j)                      (items with `shifted`)
+ * with t_j the TRIMMED length of p_j: the index of its highest non-zero coefficient below len, plus one (0 for a zero or empty
+ * polynomial) -- a device buffer is not trimmed as upstream's DensePolynomial is, so zeros at the top of len do not count against the
+ * size checks.  trimmed_len[j] = t_j (nullable), which the caller needs as the length for pcdhip_kzg_open. */
+typedef struct {
+  const pcdhip_buf* poly;              /* ABI Montgomery coefficients, low degree first; may be NULL when len == 0 */
+  uint64_t len;
+  const pcdhip_buf* blinding;          /* NULL: the commitment is not hiding */
+  uint64_t blinding_len;
+  const pcdhip_buf* shifted_blinding;  /* NULL: the shifted commitment is not hiding (non-NULL only with `shifted`) */
+  uint64_t shifted_blinding_len;
+  uint64_t shifted_offset;             /* first element of shifted_powers_of_g this item uses (upstream: max_degree - degree_bound) */
+  uint32_t shifted, _pad;              /* != 0: also produce the degree-bound ("shifted") commitment */
+} pcdhip_kzg_commit_item;
+/* Outputs: one affine point (x || y, ABI Montgomery) and one flag byte per item; the identity is flag 1 with zero coordinates, as
+ * pcdhip_to_affine writes it; items without `shifted` get flag 1 in shifted_inf.  shifted_xy / shifted_inf may be NULL when no item is
+ * shifted.  k == 0 succeeds without a launch.  PCDHIP_E_ARG (upstream's TooManyCoefficients / IncorrectDegreeBound) when t_j >
+ * powers_of_g->n, shifted_offset + t_j > shifted_powers_of_g->n, or a blinding length exceeds powers_of_gamma_g->n; the first two are
+ * found from the trimmed lengths that come back with the results, so the call then fails after the fact with no partial output
+ * guaranteed.  Also PCDHIP_E_ARG: null required pointers, len beyond the buffer's n, a buffer that is not of the curve's scalar field,
+ * handles of different curves or not G1, sharded handles, `shifted` or a blinding set while its handle (or shifted_xy / shifted_inf) is
+ * NULL, and outstanding MSM tickets (the rule of pcdhip_groth16_prove: the call uses the same side streams and workspaces). */
+int pcdhip_kzg_commit(pcdhip_ctx* ctx, const pcdhip_bases* powers_of_g, const pcdhip_bases* powers_of_gamma_g /* nullable */,
+                      const pcdhip_bases* shifted_powers_of_g /* nullable */, const pcdhip_kzg_commit_item* items, size_t k,
+                      uint64_t* comm_xy, uint8_t* comm_inf, uint64_t* shifted_xy /* nullable */, uint8_t* shifted_inf /* nullable */,
+                      uint64_t* trimmed_len /* nullable, k entries */);
 
 /* ---- K8 vector algebra for Marlin's AHP rounds ---------------------------------------------------------------------------
  * What the prover does with a polynomial between its transforms and its commitments, on device vectors of ABI Montgomery elements.

@@ -47,6 +47,13 @@ class G16PkHost(C.Structure):
                 ("l_query", C.c_void_p), ("l_inf", C.c_void_p), ("l_len", C.c_uint64)]
 
 
+class KzgCommitItem(C.Structure):
+    """Mirror of `pcdhip_kzg_commit_item` (include/pcdhip.h)."""
+    _fields_ = [("poly", C.c_void_p), ("len", C.c_uint64), ("blinding", C.c_void_p), ("blinding_len", C.c_uint64),
+                ("shifted_blinding", C.c_void_p), ("shifted_blinding_len", C.c_uint64), ("shifted_offset", C.c_uint64),
+                ("shifted", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 _LIB = None
 
 EXPORTS = [
@@ -61,7 +68,7 @@ EXPORTS = [
     "pcdhip_proof_deserialize", "pcdhip_vk_serialized_size", "pcdhip_vk_serialize", "pcdhip_vk_deserialize",
     "pcdhip_process_vk", "pcdhip_pvk_free", "pcdhip_groth16_verify_prepared", "pcdhip_groth16_verify_batch_rlc",
     "pcdhip_multi_pairing", "pcdhip_pairing_set_mode", "pcdhip_groth16_verify", "pcdhip_groth16_verify_batch", "pcdhip_timer_start", "pcdhip_timer_stop",
-    "pcdhip_poly_eval", "pcdhip_poly_lincomb", "pcdhip_poly_div_linear", "pcdhip_kzg_open", "pcdhip_kzg_check",
+    "pcdhip_poly_eval", "pcdhip_poly_lincomb", "pcdhip_poly_div_linear", "pcdhip_kzg_open", "pcdhip_kzg_check", "pcdhip_kzg_commit",
     "pcdhip_vec_mul", "pcdhip_vec_batch_inverse", "pcdhip_poly_div_vanishing", "pcdhip_poly_mul",
     "pcdhip_msm_short", "pcdhip_msm_short_dev", "pcdhip_msm_set_short",
 ]
@@ -88,6 +95,7 @@ def lib():
         _LIB.pcdhip_vec_batch_inverse.argtypes = [vp, vp, sz, vp, vp]
         _LIB.pcdhip_poly_div_vanishing.argtypes = [vp, vp, sz, sz, vp, szp, vp, szp]
         _LIB.pcdhip_poly_mul.argtypes = [vp, vp, sz, vp, sz, vp, szp]
+        _LIB.pcdhip_kzg_commit.argtypes = [vp, vp, vp, vp, C.POINTER(KzgCommitItem), sz, vp, vp, vp, vp, vp]
     return _LIB
 
 
@@ -654,6 +662,29 @@ class Context:
                                           C.c_size_t(length), blinding._h if blinding is not None else None, C.c_size_t(bl),
                                           _p(_u64(z_mont)), _p(w), _p(v), _p(rv)))
         return w, v, (rv if blinding is not None else None)
+
+    def kzg_commit(self, powers, items, powers_of_gamma_g=None, shifted_powers=None):
+        """KZG10::commit / the loop of MarlinKZG10::commit over the polynomials of one round, all on device data.  `items`: dicts with
+        `poly` (DeviceBuf of ABI Montgomery coefficients, or None for the empty polynomial) and optionally `len`, `blinding`, `blinding_len`,
+        `shifted` (bool), `shifted_offset`, `shifted_blinding`, `shifted_blinding_len` (lengths default to the buffers' n)
+        -> (comm_xy, comm_inf, shifted_xy, shifted_inf, trimmed_len), one row per item"""
+        k = len(items)
+        arr = (KzgCommitItem * max(k, 1))()
+        h = lambda b: b._h if b is not None else None
+        ln = lambda it, key, b: 0 if b is None else int(it.get(key, b.n) if it.get(key) is not None else b.n)
+        for a, it in zip(arr, items):
+            p, bl, sbl = it.get("poly"), it.get("blinding"), it.get("shifted_blinding")
+            a.poly, a.len = h(p), ln(it, "len", p)
+            a.blinding, a.blinding_len = h(bl), ln(it, "blinding_len", bl)
+            a.shifted_blinding, a.shifted_blinding_len = h(sbl), ln(it, "shifted_blinding_len", sbl)
+            a.shifted_offset, a.shifted = int(it.get("shifted_offset", 0)), 1 if it.get("shifted") else 0
+        l1 = point_limbs(powers.curve, G1)
+        comm, sh = np.zeros((k, l1), dtype=np.uint64), np.zeros((k, l1), dtype=np.uint64)
+        cinf, sinf = np.zeros(k, dtype=np.uint8), np.zeros(k, dtype=np.uint8)
+        tl = np.zeros(k, dtype=np.uint64)
+        self._check(lib().pcdhip_kzg_commit(self._ctx, powers._h, h(powers_of_gamma_g), h(shifted_powers), arr if k else None, k,
+                                            _p(comm), _p(cinf), _p(sh), _p(sinf), _p(tl)))
+        return comm, cinf, sh, sinf, tl
 
     def kzg_check(self, curve, g_xy, h_xy, beta_h_xy, comms_xy, points_mont, values_mont, w_xy, gamma_g_xy=None, random_v_mont=None,
                   randomizers_canonical=None, comms_inf=None, w_inf=None):

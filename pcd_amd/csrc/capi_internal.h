@@ -75,6 +75,9 @@ void drain_peers(pcdhip_ctx* ctx);
 
 // ---- capi_msm_short.hip (the caller has bound the device; PCDHIP_E_ARG for a sharded handle or a range beyond the vector)
 int msm_short_common(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const uint32_t* scalars_dev, size_t n, uint64_t* out_xyz);
+// the same without the copy to the host and its wait: one Jacobian point in the device image at out_dev (device memory), 1 <= n <=
+// MSM_SHORT_MAX_N; for scalars known to be reduced (the error word is not read)
+int msm_short_async(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const uint32_t* scalars_dev, size_t n, uint32_t* out_dev);
 int msm_short_host(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const uint64_t* scalars, size_t n, uint64_t* out_xyz);
 
 // ---- capi_fft.hip

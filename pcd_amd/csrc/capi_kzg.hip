@@ -1,11 +1,13 @@
-// ------------------------------------------------------------------------------------------------ K7: KZG10 open side
-// (poly.hip.h: division by (X - z), evaluation, linear combination; then the witness MSMs and the pairing check)
+// ------------------------------------------------------------------------------------------------ K7: KZG10 commit and open side
+// (poly.hip.h: canonical scalars and trimmed lengths for the commitments' MSMs; division by (X - z), evaluation, linear combination;
+//  then the witness MSMs and the pairing check)
 #include "capi_internal.h"
 
 using namespace pcd;
 
 namespace {
-enum { AUX_POLY = AUX_FB_OUT + 1, AUX_POLY_Q, AUX_POLY_R };  // descriptors | values | tile scratch;  the two quotients of an opening
+// descriptors | values | tile scratch;  the two quotients of an opening;  everything of one pcdhip_kzg_commit call
+enum { AUX_POLY = AUX_FB_OUT + 1, AUX_POLY_Q, AUX_POLY_R, AUX_COMMIT };
 
 // descriptors of k polynomials of one field (lens[j] <= their buffers' n, below 2^31) -> the field, or -1 when they do not qualify
 int poly_descs(const pcdhip_buf* const* polys, const size_t* lens, size_t k, std::vector<PolyDesc>* d, uint64_t* max_len) {
@@ -57,6 +59,111 @@ int kzg_witness(pcdhip_ctx* ctx, const pcdhip_bases* bases, const uint32_t* q_de
   }
   if (n <= ctx->msm_short_max) return msm_short_common(ctx, bases, 0, q_dev, n, out_xyz);  // pcdhip_msm_set_short: no buckets for a few pairs
   return msm_common(ctx, bases, 0, q_dev, n, out_xyz);
+}
+// One MSM of a commitment's hiding part, on the context's own stream, its Jacobian result (device image) left at `out`: without buckets
+// for a few pairs when pcdhip_msm_set_short allows it (the rule of kzg_witness), through the bucket pipeline otherwise.  Asynchronous;
+// the scalars come from poly_commit_scalars and are reduced, so no error word is read.
+int commit_hiding_msm(pcdhip_ctx* ctx, const pcdhip_bases* bases, const uint32_t* scalars_dev, size_t n, uint32_t* out) {
+  if (n <= ctx->msm_short_max) return msm_short_async(ctx, bases, 0, scalars_dev, n, out);
+  const GroupEntry& ge = group_entry(bases->curve_id, bases->group_id);
+  const size_t jac_b = (size_t)ge.point_words / 2 * 3 * 4;
+  TRY(ctx->msm_ws.ensure(WS_OUT, jac_b + 64));
+  uint32_t* out_dev = (uint32_t*)ctx->msm_ws.buf[WS_OUT];
+  TRY(ge.msm(ctx->msm_ws, ctx->stream, bases->view(0), scalars_dev, (uint32_t)n, out_dev, ctx->msm_c, ctx->msm_chunk, ctx->msm_sort, nullptr, nullptr,
+             MSM_SHARE_NONE));
+  TRY(hipMemcpyAsync(out, out_dev, jac_b, hipMemcpyDeviceToDevice, ctx->stream));
+  return PCDHIP_OK;
+}
+
+struct CommitPlan {            // what pcdhip_kzg_commit has validated, per item
+  uint64_t n = 0;              // pairs of the item's MSMs: min(len, cap)
+  size_t scal = 0;             // first element of its canonical scalars in the call's scalar area
+  int blind = -1, sblind = -1; // descriptor index of the blinding polynomials (-1: none)
+  size_t bscal = 0, sbscal = 0;
+};
+size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// Everything of the call behind its argument checks.  One scalar area holds the canonical coefficients of all k polynomials and of their
+// blinding polynomials, written by ONE launch of poly_commit_scalars on the context's stream; item j's MSMs then run on side stream
+// j mod 4 over their slice while the hiding MSMs, a few coefficients each, run on the context's stream.  No host wait before the end: the
+// MSMs cover min(len, cap) pairs and the size rule is applied to the trimmed lengths that come back with the results.
+int kzg_commit_run(pcdhip_ctx* ctx, const pcdhip_bases* pg, const pcdhip_bases* pgg, const pcdhip_bases* sp, const pcdhip_kzg_commit_item* items,
+                   size_t k, const std::vector<CommitPlan>& plan, std::vector<PolyCommitDesc>& descs, size_t scal_elems, uint64_t max_len,
+                   uint64_t* comm_xy, uint8_t* comm_inf, uint64_t* shifted_xy, uint8_t* shifted_inf, uint64_t* trimmed_len) {
+  const GroupEntry& ge = group_entry(pg->curve_id, 1);
+  const FieldEntry& fe = field_entry(kCurveFr[pg->curve_id]);
+  const size_t jw = (size_t)ge.point_words / 2 * 3, jac_b = jw * 4, jac_abi_b = (size_t)ge.point_abi_words / 2 * 3 * 4;
+  const size_t ab = (size_t)ge.point_abi_words * 4, sw = (size_t)fe.abi_words, nd = descs.size(), slots = 2 * k;
+  // descriptors | results: part 0 the large MSMs, part 1 the hiding MSMs, slot 2j item j's plain and 2j + 1 its shifted commitment |
+  // their sums | the sums in the C-ABI image | what goes back to the host: affine points, trimmed lengths | scalars
+  const size_t o_res = up256(nd * sizeof(PolyCommitDesc)), o_sum = o_res + up256(2 * slots * jac_b), o_abi = o_sum + up256(slots * jac_b);
+  const size_t o_back = o_abi + up256(slots * jac_abi_b), back_b = slots * ab + nd * 4, o_scal = o_back + up256(back_b);
+  TRY(ctx->aux_ws.ensure(AUX_COMMIT, o_scal + std::max<size_t>(scal_elems, 1) * sw * 4));
+  char* base = (char*)ctx->aux_ws.buf[AUX_COMMIT];
+  uint32_t* res = (uint32_t*)(base + o_res);
+  uint32_t* scal = (uint32_t*)(base + o_scal);
+  uint32_t* trimmed_dev = (uint32_t*)(base + o_back + slots * ab);
+  for (size_t j = 0; j < k; j++) {
+    descs[j].out = scal + plan[j].scal * sw;
+    if (plan[j].blind >= 0) descs[plan[j].blind].out = scal + plan[j].bscal * sw;
+    if (plan[j].sblind >= 0) descs[plan[j].sblind].out = scal + plan[j].sbscal * sw;
+  }
+  hipStream_t st = ctx->stream;
+  TRY(hipMemcpyAsync(base, descs.data(), nd * sizeof(PolyCommitDesc), hipMemcpyHostToDevice, st));
+  TRY(hipMemsetAsync(res, 0, 2 * slots * jac_b, st));  // (all zeros: Z = 0, the identity -- what an item without that part contributes)
+  TRY(hipMemsetAsync(trimmed_dev, 0, nd * 4, st));
+  TRY(fe.poly_commit_scalars(st, (const PolyCommitDesc*)base, (uint32_t)nd, max_len, trimmed_dev));
+  TRY(hipEventRecord(ctx->g16_ready, st));
+  bool used[pcdhip_ctx::PIPE_SLOTS] = {};
+  for (size_t j = 0; j < k; j++) {
+    if (plan[j].n == 0) continue;
+    const int s = (int)(j % pcdhip_ctx::PIPE_SLOTS);
+    MsmWorkspace& ws = ctx->g16_ws[2 + s];
+    hipStream_t sk = ctx->g16_streams[2 + s];
+    if (!used[s]) TRY(hipStreamWaitEvent(sk, ctx->g16_ready, 0));
+    used[s] = true;
+    TRY(ws.ensure(WS_OUT, jac_b + 64));
+    uint32_t* out_dev = (uint32_t*)ws.buf[WS_OUT];
+    for (int sh = 0; sh < (items[j].shifted ? 2 : 1); sh++) {
+      const MsmBasesView bv = sh ? sp->view((size_t)items[j].shifted_offset) : pg->view(0);
+      ws.lane = ctx->g16_schedule == 2 && ctx->pipe_lane && ctx->lane.stream ? &ctx->lane : nullptr;
+      const hipError_t me = ge.msm(ws, sk, bv, scal + plan[j].scal * sw, (uint32_t)plan[j].n, out_dev, ctx->msm_c, ctx->msm_chunk, ctx->msm_sort,
+                                   nullptr, nullptr, MSM_SHARE_NONE);
+      ws.lane = nullptr;
+      TRY(me);
+      TRY(hipMemcpyAsync(res + (2 * j + sh) * jw, out_dev, jac_b, hipMemcpyDeviceToDevice, sk));  // (before the workspace is used again)
+    }
+    TRY(hipEventRecord(ctx->g16_end[2 + s], sk));
+  }
+  for (size_t j = 0; j < k; j++) {
+    int rc = PCDHIP_OK;
+    if (plan[j].blind >= 0 && items[j].blinding_len)
+      rc = commit_hiding_msm(ctx, pgg, scal + plan[j].bscal * sw, (size_t)items[j].blinding_len, res + (slots + 2 * j) * jw);
+    if (!rc && plan[j].sblind >= 0 && items[j].shifted_blinding_len)
+      rc = commit_hiding_msm(ctx, pgg, scal + plan[j].sbscal * sw, (size_t)items[j].shifted_blinding_len, res + (slots + 2 * j + 1) * jw);
+    if (rc) return rc;
+  }
+  for (int s = 0; s < pcdhip_ctx::PIPE_SLOTS; s++) if (used[s]) TRY(hipStreamWaitEvent(st, ctx->g16_end[2 + s], 0));
+  TRY(ge.jac_sum_parts(st, res, slots * jw, 2, (uint32_t)slots, (uint32_t*)(base + o_sum)));
+  TRY(ge.jac_out(st, (const uint32_t*)(base + o_sum), (uint32_t)slots, (uint32_t*)(base + o_abi)));
+  TRY(ge.to_affine(st, (const uint32_t*)(base + o_abi), (uint32_t)slots, (uint32_t*)(base + o_back)));
+  std::vector<uint64_t> back((back_b + 7) / 8);
+  TRY(hipMemcpyAsync(back.data(), base + o_back, back_b, hipMemcpyDeviceToHost, st));
+  TRY(hipStreamSynchronize(st));
+  const uint32_t* t = (const uint32_t*)((const char*)back.data() + slots * ab);
+  // upstream's TooManyCoefficients / IncorrectDegreeBound, on the trimmed lengths
+  for (size_t j = 0; j < k; j++)
+    if (t[j] > pg->n || (items[j].shifted && items[j].shifted_offset + t[j] > sp->n)) return PCDHIP_E_ARG;
+  const size_t pl = ab / 8;
+  auto is_identity = [&](const uint64_t* p) { uint64_t o = 0; for (size_t i = 0; i < pl; i++) o |= p[i]; return o == 0 ? 1 : 0; };
+  for (size_t j = 0; j < k; j++) {
+    memcpy(comm_xy + j * pl, &back[2 * j * pl], ab);
+    comm_inf[j] = (uint8_t)is_identity(&back[2 * j * pl]);
+    if (shifted_xy) memcpy(shifted_xy + j * pl, &back[(2 * j + 1) * pl], ab);  // (zeros for an item without a degree bound)
+    if (shifted_inf) shifted_inf[j] = items[j].shifted ? (uint8_t)is_identity(&back[(2 * j + 1) * pl]) : 1;
+    if (trimmed_len) trimmed_len[j] = t[j];
+  }
+  return PCDHIP_OK;
 }
 void mont_to_canonical(int fr, const uint64_t* in, uint64_t* out) {
   with_host_field(fr, [&](auto f) { decltype(f)::type::from_abi((const uint32_t*)in).to_canonical_words((uint32_t*)out); });
@@ -151,6 +258,57 @@ int pcdhip_kzg_open(pcdhip_ctx* ctx, const pcdhip_bases* powers_of_g, const pcdh
   rc = kzg_divide(ctx, blinding, blinding_len, z_mont, AUX_POLY_R, &rq, random_v_mont);
   rc = rc ? rc : kzg_witness(ctx, powers_of_gamma_g, rq, bqn, &both[jw]);
   return rc ? rc : pcdhip_points_sum(ctx, powers_of_g->curve_id, powers_of_g->group_id, both.data(), 2, w_xyz_mont);
+  });
+}
+
+int pcdhip_kzg_commit(pcdhip_ctx* ctx, const pcdhip_bases* powers_of_g, const pcdhip_bases* powers_of_gamma_g,
+                      const pcdhip_bases* shifted_powers_of_g, const pcdhip_kzg_commit_item* items, size_t k, uint64_t* comm_xy, uint8_t* comm_inf,
+                      uint64_t* shifted_xy, uint8_t* shifted_inf, uint64_t* trimmed_len) {
+  return guarded([&]() -> int {
+  if (!ctx || !powers_of_g || (k && (!items || !comm_xy || !comm_inf))) return PCDHIP_E_ARG;  // (before any handle is looked into)
+  const pcdhip_bases *pg = powers_of_g, *pgg = powers_of_gamma_g, *sp = shifted_powers_of_g;
+  auto g1_of_pg = [&](const pcdhip_bases* b) { return b->shards.empty() && b->group_id == 1 && b->curve_id == pg->curve_id; };
+  if (!valid_curve(pg->curve_id) || !g1_of_pg(pg) || (pgg && !g1_of_pg(pgg)) || (sp && !g1_of_pg(sp)) || k > 21845) return PCDHIP_E_ARG;
+  if (pipe_pending(ctx)) return PCDHIP_E_ARG;  // submitted MSMs still own side-stream workspaces: collect them first
+  if (k == 0) return PCDHIP_OK;
+  const int fr = kCurveFr[pg->curve_id];
+  std::vector<CommitPlan> plan(k);
+  std::vector<PolyCommitDesc> descs(k);
+  size_t scal_elems = 0;
+  uint64_t max_len = 0;
+  auto blinding_ok = [&](const pcdhip_buf* b, uint64_t len) { return pgg && b->field_id == fr && len <= b->n && len <= pgg->n; };
+  for (size_t j = 0; j < k; j++) {
+    const pcdhip_kzg_commit_item& it = items[j];
+    if ((!it.poly && it.len) || (it.poly && (it.poly->field_id != fr || it.len > it.poly->n)) || it.len >= (1ull << 31)) return PCDHIP_E_ARG;
+    if (it.blinding && !blinding_ok(it.blinding, it.blinding_len)) return PCDHIP_E_ARG;
+    if (it.shifted_blinding && (!it.shifted || !blinding_ok(it.shifted_blinding, it.shifted_blinding_len))) return PCDHIP_E_ARG;
+    if (it.shifted && (!sp || !shifted_xy || !shifted_inf || it.shifted_offset > sp->n)) return PCDHIP_E_ARG;
+    const uint64_t cap = it.shifted ? std::min<uint64_t>(pg->n, sp->n - it.shifted_offset) : pg->n;  // bases the item may use
+    plan[j].n = std::min<uint64_t>(it.len, cap);
+    plan[j].scal = scal_elems;
+    scal_elems += plan[j].n;
+    descs[j] = {it.poly ? it.poly->dptr : nullptr, it.len, cap, nullptr};
+    max_len = std::max(max_len, it.len);
+  }
+  for (size_t j = 0; j < k; j++) {  // the blinding polynomials: further descriptors of the same launch
+    const pcdhip_kzg_commit_item& it = items[j];
+    if (it.blinding && it.blinding_len) {
+      plan[j].blind = (int)descs.size(); plan[j].bscal = scal_elems; scal_elems += it.blinding_len;
+      descs.push_back({it.blinding->dptr, it.blinding_len, it.blinding_len, nullptr});
+      max_len = std::max(max_len, it.blinding_len);
+    }
+    if (it.shifted_blinding && it.shifted_blinding_len) {
+      plan[j].sblind = (int)descs.size(); plan[j].sbscal = scal_elems; scal_elems += it.shifted_blinding_len;
+      descs.push_back({it.shifted_blinding->dptr, it.shifted_blinding_len, it.shifted_blinding_len, nullptr});
+      max_len = std::max(max_len, it.shifted_blinding_len);
+    }
+  }
+  BIND();
+  int rc = ensure_side_streams(ctx);
+  if (rc) return rc;
+  rc = kzg_commit_run(ctx, pg, pgg, sp, items, k, plan, descs, scal_elems, max_len, comm_xy, comm_inf, shifted_xy, shifted_inf, trimmed_len);
+  if (rc) (void)hipDeviceSynchronize();  // (an error partway: nothing of this call stays in flight on the side streams, or reads the frames above)
+  return rc;
   });
 }
 

@@ -33,6 +33,15 @@ int msm_short_common(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, 
   TRY(hipStreamSynchronize(ctx->stream));
   return too_wide ? PCDHIP_E_ARG : PCDHIP_OK;
 }
+int msm_short_async(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const uint32_t* scalars_dev, size_t n, uint32_t* out_dev) {
+  if (!bases->shards.empty() || offset > bases->n || n > bases->n - offset || n == 0) return PCDHIP_E_ARG;
+  if (n > MSM_SHORT_MAX_N) return PCDHIP_E_SIZE_UNSUPPORTED;
+  const GroupEntry& ge = group_entry(bases->curve_id, bases->group_id);
+  const MsmBasesView bv = bases->view(offset);
+  TRY(ctx->short_ws.ensure(SHORT_SCRATCH, ge.msm_short_scratch_words(bv, (uint32_t)n) * 4));
+  TRY(ge.msm_short(ctx->stream, bv, scalars_dev, (uint32_t)n, (uint32_t*)ctx->short_ws.buf[SHORT_SCRATCH], out_dev));
+  return PCDHIP_OK;
+}
 int msm_short_host(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const uint64_t* scalars, size_t n, uint64_t* out_xyz) {
   if (!bases->shards.empty()) return PCDHIP_E_ARG;
   if (n > MSM_SHORT_MAX_N) return PCDHIP_E_SIZE_UNSUPPORTED;

@@ -193,6 +193,9 @@ const GroupEntry& group_entry(int curve_id, int group_id);  // group_id 1 / 2
 // ---- per-field entries (inst_field.hip) ------------------------------------------------------------
 // one polynomial of the K7 kernels (poly.hip.h): `len` coefficients in the C-ABI Montgomery image, low degree first
 struct PolyDesc { const uint32_t* p; uint64_t len; };
+// one polynomial of the commit side (poly.hip.h poly_commit_scalars): a PolyDesc, the number of bases its MSM may use, and where its
+// canonical scalars go (min(len, cap) of them)
+struct PolyCommitDesc { const uint32_t* p; uint64_t len; uint64_t cap; uint32_t* out; };
 struct FieldEntry {
   int words;      // u32 words per element, device-internal image
   int abi_words;  // u32 words per element at the C-ABI
@@ -246,6 +249,10 @@ struct FieldEntry {
   hipError_t (*vec_batch_inverse)(hipStream_t, const uint32_t* in, uint64_t n, const uint32_t* scale_abi, uint32_t* out);
   // p = q (X^n - 1) + r: len - n coefficients of q (none for len <= n), min(len, n) of r (r may be null); q, r distinct from p
   hipError_t (*poly_div_vanishing)(hipStream_t, const uint32_t* p, uint64_t len, uint64_t n, uint32_t* q, uint32_t* r);
+  // K7 commit side (poly.hip.h): the canonical words of the coefficients i < min(len_j, cap_j) of the k polynomials of descs_dev, and
+  // trimmed_dev[j] = the index of polynomial j's highest non-zero coefficient below len_j, plus one (k words, ZEROED by the caller on the
+  // stream before the launch; a zero or empty polynomial leaves 0)
+  hipError_t (*poly_commit_scalars)(hipStream_t, const PolyCommitDesc* descs_dev, uint32_t k, uint64_t max_len, uint32_t* trimmed_dev);
 };
 const FieldEntry& field_entry(int field_id);
 

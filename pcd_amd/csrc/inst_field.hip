@@ -494,6 +494,19 @@ hipError_t poly_lincomb_run(hipStream_t st, const PolyDesc* descs_dev, const uin
   return hipGetLastError();
 }
 
+// ---- K7 commit side (poly.hip.h): canonical scalars and trimmed lengths of k polynomials, one launch
+hipError_t poly_commit_scalars_run(hipStream_t st, const PolyCommitDesc* descs_dev, uint32_t k, uint64_t max_len, uint32_t* trimmed_dev) {
+  if (k == 0 || max_len == 0) return hipSuccess;
+  if (k > 65535 || max_len >= (1ull << 31)) return hipErrorInvalidValue;
+  FTP cin, one_raw = FTP::zero();
+  for (int i = 0; i < FTP::N; i++) cin.v[i] = FTP::Params::cin(i);
+  one_raw.v[0] = 1;
+  const FTP kc = cin * one_raw;
+  hipLaunchKernelGGL(poly_commit_scalars<FTP>, dim3((uint32_t)((max_len + POLY_COMMIT_B - 1) / POLY_COMMIT_B), k), dim3(POLY_COMMIT_B), 0, st,
+                     descs_dev, kc, trimmed_dev);
+  return hipGetLastError();
+}
+
 // ---- K8 vector algebra (poly.hip.h): batch inversion, pointwise product, division by X^n - 1
 hipError_t vec_mul_run(hipStream_t st, const uint32_t* a, const uint32_t* b, uint64_t n, uint32_t* out, int abi) {
   if (n == 0) return hipSuccess;
@@ -528,7 +541,7 @@ const FieldEntry* PCD_CAT(pcd_field_entry_, PCD_FIELD_IDX)() {
   static const FieldEntry e = {EW, FT::ABI_WORDS, FT::Params::TWO_ADICITY, make_tables, run, convert, spmv, small_abi, mul_sub_divz,
                                mixed_make_tables, mixed_run, mixed_mul_sub_divz, scale_canon, SETUP_CONSTS, setup_scalars, run_batched_entry, spmv3,
                                poly_scratch_words, poly_eval, poly_lincomb_run, vec_mul_run, vec_batch_inverse_run,
-                               poly_div_vanishing_run};
+                               poly_div_vanishing_run, poly_commit_scalars_run};
   return &e;
 }
 

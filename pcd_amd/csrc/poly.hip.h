@@ -206,6 +206,36 @@ __global__ void __launch_bounds__(256) poly_lincomb(const PolyDesc* __restrict__
   if (i < n_out) acc.canonical().pack32(out + i * AW);
 }
 
+// ---- K7 commit side (ark-poly-commit `KZG10::commit`): the canonical scalars of k polynomials for their MSMs, and their trimmed lengths.
+// One lane per coefficient, one polynomial per blockIdx.y.  x = (x R) (R' / R) / R' is one product with the constant kc = cin * 1 (as in
+// poly_div_tile<F, true>), which the host forms once and passes by value.  Coefficients at i >= cap are reduced and inspected only: they
+// have no base, but they still count for the trimmed length, from which the caller makes its size checks after the fact.  Nothing at
+// i >= len is read.  trimmed[y] is raised by one atomicMax per workgroup that holds a non-zero coefficient.
+constexpr int POLY_COMMIT_B = 256;
+template <class F>
+__global__ void __launch_bounds__(POLY_COMMIT_B) poly_commit_scalars(const PolyCommitDesc* __restrict__ descs, const F kc,
+                                                                     uint32_t* __restrict__ trimmed) {
+  constexpr int B = POLY_COMMIT_B, AW = F::ABI_WORDS;
+  __shared__ uint32_t top;
+  const PolyCommitDesc d = descs[blockIdx.y];
+  const uint64_t lo = (uint64_t)blockIdx.x * B;
+  if (lo >= d.len) return;  // (whole workgroup)
+  if (threadIdx.x == 0) top = 0;
+  __syncthreads();
+  const uint64_t i = lo + threadIdx.x;
+  uint32_t mine = 0;
+  if (i < d.len) {
+    const F x = (F::unpack32(d.p + i * AW) * kc).canonical();
+    if (!x.is_raw_zero()) mine = (uint32_t)i + 1;
+    if (i < d.cap) x.pack32(d.out + i * AW);
+  }
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) mine = max(mine, (uint32_t)__shfl_xor((int)mine, s, 64));
+  if ((threadIdx.x & 63) == 0 && mine) atomicMax(&top, mine);
+  __syncthreads();
+  if (threadIdx.x == 0 && top) atomicMax(trimmed + blockIdx.y, top);
+}
+
 // ---- K8, vector algebra for Marlin's AHP rounds: batch inversion (ark-ff `batch_inversion[_and_mul]`), the pointwise product, division
 // by the vanishing polynomial X^n - 1 (ark-poly `divide_by_vanishing_poly`).  ABI Montgomery words in and out, as above.
 //

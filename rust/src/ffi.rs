@@ -24,6 +24,12 @@ pub struct pcdhip_g16_setup_out {
     pub h_query: *mut u64, pub h_inf: *mut u8, pub l_query: *mut u64, pub l_inf: *mut u8, pub gamma_abc_g1: *mut u64, pub gamma_abc_inf: *mut u8,
     pub domain_size: u64,
 }
+/// one labeled polynomial of `pcdhip_kzg_commit` (KZG10::commit / MarlinKZG10::commit over device-resident coefficients)
+#[repr(C)]
+pub struct pcdhip_kzg_commit_item {
+    pub poly: *const pcdhip_buf, pub len: u64, pub blinding: *const pcdhip_buf, pub blinding_len: u64,
+    pub shifted_blinding: *const pcdhip_buf, pub shifted_blinding_len: u64, pub shifted_offset: u64, pub shifted: u32, pub _pad: u32,
+}
 
 extern "C" {
     pub fn pcdhip_strerror(code: c_int) -> *const c_char;
@@ -80,6 +86,10 @@ extern "C" {
                                      r: *mut pcdhip_buf, r_len: *mut usize) -> c_int;
     pub fn pcdhip_poly_mul(ctx: *mut pcdhip_ctx, a: *const pcdhip_buf, la: usize, b: *const pcdhip_buf, lb: usize, out: *mut pcdhip_buf,
                            out_len: *mut usize) -> c_int;
+    // K7 commit side: KZG10::commit / the loop of MarlinKZG10::commit, polynomials and blinding polynomials resident on the device
+    pub fn pcdhip_kzg_commit(ctx: *mut pcdhip_ctx, powers_of_g: *const pcdhip_bases, powers_of_gamma_g: *const pcdhip_bases,
+                             shifted_powers_of_g: *const pcdhip_bases, items: *const pcdhip_kzg_commit_item, k: usize, comm_xy: *mut u64,
+                             comm_inf: *mut u8, shifted_xy: *mut u64, shifted_inf: *mut u8, trimmed_len: *mut u64) -> c_int;
 }
 
 /// `PCDHIP_E_*` (include/pcdhip.h)
