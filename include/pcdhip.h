@@ -110,9 +110,29 @@ int pcdhip_msm_short(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, 
                      size_t n, uint64_t* out_xyz_mont);
 int pcdhip_msm_short_dev(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const pcdhip_buf* scalars,
                          size_t scalar_offset, size_t n, uint64_t* out_xyz_mont);
+/* k independent short MSMs over ONE handle as one launch chain: the hiding MSMs of a commit round, the vectors of a batch check, a
+ * verifier's linear combinations of commitments.  One after the other, k short MSMs cost k serial chains of doublings on one wave
+ * each; here every MSM gets its own wave of the same two or three launches, so the call costs about one chain.  Item j is
+ *   out[j] = MSM(bases[base_offset .. base_offset + n), scalars[scalar_offset .. scalar_offset + n))
+ * with the encodings and the result of pcdhip_msm_short: k Jacobian points X || Y || Z one behind the other, Z = 0 for the identity
+ * (n == 0 gives it), the same affine image as pcdhip_msm.  Items may overlap and repeat; everything is read only.  The host form
+ * uploads its scalars_n scalars once; the _dev form reads a resident buffer.  k == 0 succeeds without a launch; k > 1024 or an item
+ * with n > 1024 gives PCDHIP_E_SIZE_UNSUPPORTED; PCDHIP_E_ARG for null pointers, an item's range beyond the handle or the scalars, a
+ * buffer that is not of the curve's scalar field, sharded bases, and an unreduced scalar in ANY item -- the call then fails as a whole
+ * (no result is valid) and the next call is clean.  One wait at the end, one copy back for all k. */
+typedef struct {
+  uint64_t base_offset;    /* first point of `bases` this MSM uses */
+  uint64_t scalar_offset;  /* first element of the scalar array / buffer */
+  uint64_t n;              /* pairs, 0 .. 1024; 0 gives the identity */
+} pcdhip_msm_short_item;
+int pcdhip_msm_short_batch(pcdhip_ctx* ctx, const pcdhip_bases* bases, const uint64_t* scalars_canonical, size_t scalars_n,
+                           const pcdhip_msm_short_item* items, size_t k, uint64_t* out_xyz_mont /* k Jacobian points */);
+int pcdhip_msm_short_batch_dev(pcdhip_ctx* ctx, const pcdhip_bases* bases, const pcdhip_buf* scalars,
+                               const pcdhip_msm_short_item* items, size_t k, uint64_t* out_xyz_mont);
 /* Opt-in routing: with max_n > 0 the witness MSMs of pcdhip_kzg_open and the two MSMs of pcdhip_kzg_check take the short path when
- * they cover at most max_n pairs (at most 1024).  Default 0: never -- those functions then run exactly the code they ran before.
- * Vectors uploaded through a multi-device context are sharded and keep the bucket pipeline. */
+ * they cover at most max_n pairs (at most 1024), and the hiding MSMs of pcdhip_kzg_commit of at most max_n coefficients run as ONE
+ * batched chain (pcdhip_msm_short_batch's kernels) instead of one bucket pipeline each.  Default 0: never -- those functions then run
+ * exactly the code they ran before.  Vectors uploaded through a multi-device context are sharded and keep the bucket pipeline. */
 int pcdhip_msm_set_short(pcdhip_ctx* ctx, size_t max_n);
 /* Throughput form of pcdhip_msm_dev for a caller with several INDEPENDENT MSMs to make (the commitments of a Marlin round over one
  * resident committer key, BASELINE configs[3]; consecutive steps of a benchmark): submit enqueues the MSM on one of the context's four
@@ -501,6 +521,11 @@ int pcdhip_kzg_commit(pcdhip_ctx* ctx, const pcdhip_bases* powers_of_g, const pc
                       const pcdhip_bases* shifted_powers_of_g /* nullable */, const pcdhip_kzg_commit_item* items, size_t k,
                       uint64_t* comm_xy, uint8_t* comm_inf, uint64_t* shifted_xy /* nullable */, uint8_t* shifted_inf /* nullable */,
                       uint64_t* trimmed_len /* nullable, k entries */);
+/* Which path the last pcdhip_kzg_commit of this context took: out[0] = large MSMs run (one per non-empty polynomial, two with a
+ * degree bound), out[1] = hiding MSMs that ran in the batched short chain (pcdhip_msm_set_short; at most 1024 of a call), out[2] = hiding
+ * MSMs that ran one at a time (the bucket pipeline -- all of them under the default), out[3] = kernel launches of the batched chain
+ * (2, or 3 when an MSM's planes take several workgroups; 0 without a batch). */
+int pcdhip_kzg_commit_last_plan(pcdhip_ctx* ctx, uint64_t out[4]);
 
 /* ---- K8 vector algebra for Marlin's AHP rounds ---------------------------------------------------------------------------
  * What the prover does with a polynomial between its transforms and its commitments, on device vectors of ABI Montgomery elements.

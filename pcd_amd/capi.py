@@ -54,6 +54,11 @@ class KzgCommitItem(C.Structure):
                 ("shifted", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class MsmShortItem(C.Structure):
+    """Mirror of `pcdhip_msm_short_item` (include/pcdhip.h)."""
+    _fields_ = [("base_offset", C.c_uint64), ("scalar_offset", C.c_uint64), ("n", C.c_uint64)]
+
+
 _LIB = None
 
 EXPORTS = [
@@ -71,6 +76,7 @@ EXPORTS = [
     "pcdhip_poly_eval", "pcdhip_poly_lincomb", "pcdhip_poly_div_linear", "pcdhip_kzg_open", "pcdhip_kzg_check", "pcdhip_kzg_commit",
     "pcdhip_vec_mul", "pcdhip_vec_batch_inverse", "pcdhip_poly_div_vanishing", "pcdhip_poly_mul",
     "pcdhip_msm_short", "pcdhip_msm_short_dev", "pcdhip_msm_set_short",
+    "pcdhip_msm_short_batch", "pcdhip_msm_short_batch_dev", "pcdhip_kzg_commit_last_plan",
 ]
 
 
@@ -96,6 +102,8 @@ def lib():
         _LIB.pcdhip_poly_div_vanishing.argtypes = [vp, vp, sz, sz, vp, szp, vp, szp]
         _LIB.pcdhip_poly_mul.argtypes = [vp, vp, sz, vp, sz, vp, szp]
         _LIB.pcdhip_kzg_commit.argtypes = [vp, vp, vp, vp, C.POINTER(KzgCommitItem), sz, vp, vp, vp, vp, vp]
+        _LIB.pcdhip_msm_short_batch.argtypes = [vp, vp, vp, sz, C.POINTER(MsmShortItem), sz, vp]
+        _LIB.pcdhip_msm_short_batch_dev.argtypes = [vp, vp, vp, C.POINTER(MsmShortItem), sz, vp]
     return _LIB
 
 
@@ -192,8 +200,25 @@ class Context:
             self._check(lib().pcdhip_msm_short(self._ctx, bases._h, C.c_size_t(offset), _p(scalars), C.c_size_t(n), _p(out)))
         return out
 
+    def msm_short_batch(self, bases, scalars, items):
+        """k independent short MSMs over one handle as one launch chain (pcdhip_msm_short_batch / _dev).  `items`: (base_offset,
+        scalar_offset, n) tuples, n pairs each from those positions on; `scalars`: canonical limbs (numpy, uploaded once) or a DeviceBuf
+        -> a (k, limbs) array of Jacobian points X||Y||Z, Z = 0 for the identity (which n == 0 gives)."""
+        k = len(items)
+        arr = (MsmShortItem * max(k, 1))()
+        for a, (bo, so, n) in zip(arr, items):
+            a.base_offset, a.scalar_offset, a.n = int(bo), int(so), int(n)
+        out = np.zeros((k, 3 * point_limbs(bases.curve, bases.group) // 2), dtype=np.uint64)
+        if isinstance(scalars, DeviceBuf):
+            self._check(lib().pcdhip_msm_short_batch_dev(self._ctx, bases._h, scalars._h, arr if k else None, k, _p(out)))
+        else:
+            scalars = _u64(scalars)
+            self._check(lib().pcdhip_msm_short_batch(self._ctx, bases._h, _p(scalars), scalars.shape[0], arr if k else None, k, _p(out)))
+        return out
+
     def msm_set_short(self, max_n):
-        """kzg_open / kzg_check run their MSMs over at most `max_n` pairs through msm_short (0, the default: never)."""
+        """kzg_open / kzg_check run their MSMs over at most `max_n` pairs through msm_short, and kzg_commit its hiding MSMs of at most
+        `max_n` coefficients as one msm_short_batch chain (0, the default: never)."""
         self._check(lib().pcdhip_msm_set_short(self._ctx, C.c_size_t(int(max_n))))
 
     def msm_submit(self, bases, scalars, offset=0, n=None, scalar_offset=0):
@@ -685,6 +710,13 @@ class Context:
         self._check(lib().pcdhip_kzg_commit(self._ctx, powers._h, h(powers_of_gamma_g), h(shifted_powers), arr if k else None, k,
                                             _p(comm), _p(cinf), _p(sh), _p(sinf), _p(tl)))
         return comm, cinf, sh, sinf, tl
+
+    def kzg_commit_last_plan(self):
+        """(large MSMs run, hiding MSMs in the batched short chain, hiding MSMs one at a time, launches of that chain) of the last
+        kzg_commit"""
+        out = (C.c_uint64 * 4)()
+        self._check(lib().pcdhip_kzg_commit_last_plan(self._ctx, out))
+        return tuple(int(v) for v in out)
 
     def kzg_check(self, curve, g_xy, h_xy, beta_h_xy, comms_xy, points_mont, values_mont, w_xy, gamma_g_xy=None, random_v_mont=None,
                   randomizers_canonical=None, comms_inf=None, w_inf=None):

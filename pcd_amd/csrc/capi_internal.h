@@ -79,6 +79,12 @@ int msm_short_common(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, 
 // MSM_SHORT_MAX_N; for scalars known to be reduced (the error word is not read)
 int msm_short_async(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const uint32_t* scalars_dev, size_t n, uint32_t* out_dev);
 int msm_short_host(pcdhip_ctx* ctx, const pcdhip_bases* bases, size_t offset, const uint64_t* scalars, size_t n, uint64_t* out_xyz);
+// k independent short MSMs over one handle as ONE chain of at most three launches on the context's stream (msm_short.hip.h, "the batched
+// form"): item j's Jacobian point (device image) lands at out_dev + items[j].out_slot * out_stride_words; the slot of an item with n == 0
+// is left as it is (the caller has zeroed it).  Asynchronous, no host wait: the descriptor table is staged by one hipMemcpyAsync into
+// ctx->short_ws, whose first word is the call's error word afterwards (*err_dev, optional).  Any k; *launches (optional) = kernels launched
+int msm_short_batch_async(pcdhip_ctx* ctx, const pcdhip_bases* bases, const MsmShortBatchIn* items, size_t k, uint32_t* out_dev,
+                          size_t out_stride_words, const uint32_t** err_dev = nullptr, uint32_t* launches = nullptr);
 
 // ---- capi_fft.hip
 int pick_domain(int field_id, size_t min_size, Dom* d);

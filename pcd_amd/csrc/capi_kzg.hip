@@ -2,6 +2,7 @@
 // (poly.hip.h: canonical scalars and trimmed lengths for the commitments' MSMs; division by (X - z), evaluation, linear combination;
 //  then the witness MSMs and the pairing check)
 #include "capi_internal.h"
+#include "msm_short.hip.h"
 
 using namespace pcd;
 
@@ -87,6 +88,11 @@ size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 // blinding polynomials, written by ONE launch of poly_commit_scalars on the context's stream; item j's MSMs then run on side stream
 // j mod 4 over their slice while the hiding MSMs, a few coefficients each, run on the context's stream.  No host wait before the end: the
 // MSMs cover min(len, cap) pairs and the size rule is applied to the trimmed lengths that come back with the results.
+// Under pcdhip_msm_set_short the hiding MSMs of at most that many pairs do not queue one behind the other: they are collected into ONE
+// msm_short_batch_async (one chain of two or three launches, a wave per MSM) that writes straight into their slots of `res`; only the
+// first HIDING_BATCH_MAX of a call, the rest and the longer ones go one at a time through commit_hiding_msm.  ctx->kzg_commit_plan says
+// which path ran (pcdhip_kzg_commit_last_plan).
+constexpr size_t HIDING_BATCH_MAX = 1024;
 int kzg_commit_run(pcdhip_ctx* ctx, const pcdhip_bases* pg, const pcdhip_bases* pgg, const pcdhip_bases* sp, const pcdhip_kzg_commit_item* items,
                    size_t k, const std::vector<CommitPlan>& plan, std::vector<PolyCommitDesc>& descs, size_t scal_elems, uint64_t max_len,
                    uint64_t* comm_xy, uint8_t* comm_inf, uint64_t* shifted_xy, uint8_t* shifted_inf, uint64_t* trimmed_len) {
@@ -115,6 +121,7 @@ int kzg_commit_run(pcdhip_ctx* ctx, const pcdhip_bases* pg, const pcdhip_bases* 
   TRY(fe.poly_commit_scalars(st, (const PolyCommitDesc*)base, (uint32_t)nd, max_len, trimmed_dev));
   TRY(hipEventRecord(ctx->g16_ready, st));
   bool used[pcdhip_ctx::PIPE_SLOTS] = {};
+  uint64_t large = 0;
   for (size_t j = 0; j < k; j++) {
     if (plan[j].n == 0) continue;
     const int s = (int)(j % pcdhip_ctx::PIPE_SLOTS);
@@ -131,18 +138,37 @@ int kzg_commit_run(pcdhip_ctx* ctx, const pcdhip_bases* pg, const pcdhip_bases* 
                                    nullptr, nullptr, MSM_SHARE_NONE);
       ws.lane = nullptr;
       TRY(me);
+      large++;
       TRY(hipMemcpyAsync(res + (2 * j + sh) * jw, out_dev, jac_b, hipMemcpyDeviceToDevice, sk));  // (before the workspace is used again)
     }
     TRY(hipEventRecord(ctx->g16_end[2 + s], sk));
   }
+  std::vector<MsmShortBatchIn> batch;  // (stays empty under the default pcdhip_msm_set_short(ctx, 0): every length is at least 1)
+  uint64_t one_by_one = 0;
+  auto hiding = [&](const uint32_t* scalars_dev, uint64_t n, size_t slot) -> int {
+    if (n <= ctx->msm_short_max && batch.size() < HIDING_BATCH_MAX) {
+      batch.push_back({scalars_dev, 0u, (uint32_t)n, (uint32_t)slot});
+      return PCDHIP_OK;
+    }
+    one_by_one++;
+    return commit_hiding_msm(ctx, pgg, scalars_dev, (size_t)n, res + slot * jw);
+  };
   for (size_t j = 0; j < k; j++) {
     int rc = PCDHIP_OK;
-    if (plan[j].blind >= 0 && items[j].blinding_len)
-      rc = commit_hiding_msm(ctx, pgg, scal + plan[j].bscal * sw, (size_t)items[j].blinding_len, res + (slots + 2 * j) * jw);
+    if (plan[j].blind >= 0 && items[j].blinding_len) rc = hiding(scal + plan[j].bscal * sw, items[j].blinding_len, slots + 2 * j);
     if (!rc && plan[j].sblind >= 0 && items[j].shifted_blinding_len)
-      rc = commit_hiding_msm(ctx, pgg, scal + plan[j].sbscal * sw, (size_t)items[j].shifted_blinding_len, res + (slots + 2 * j + 1) * jw);
+      rc = hiding(scal + plan[j].sbscal * sw, items[j].shifted_blinding_len, slots + 2 * j + 1);
     if (rc) return rc;
   }
+  uint32_t chain = 0;
+  if (!batch.empty()) {  // (the scalars come from poly_commit_scalars and are reduced: no error word is read)
+    int rc = msm_short_batch_async(ctx, pgg, batch.data(), batch.size(), res, jw, nullptr, &chain);
+    if (rc) return rc;
+  }
+  ctx->kzg_commit_plan[0] = large;
+  ctx->kzg_commit_plan[1] = batch.size();
+  ctx->kzg_commit_plan[2] = one_by_one;
+  ctx->kzg_commit_plan[3] = chain;
   for (int s = 0; s < pcdhip_ctx::PIPE_SLOTS; s++) if (used[s]) TRY(hipStreamWaitEvent(st, ctx->g16_end[2 + s], 0));
   TRY(ge.jac_sum_parts(st, res, slots * jw, 2, (uint32_t)slots, (uint32_t*)(base + o_sum)));
   TRY(ge.jac_out(st, (const uint32_t*)(base + o_sum), (uint32_t)slots, (uint32_t*)(base + o_abi)));
@@ -310,6 +336,12 @@ int pcdhip_kzg_commit(pcdhip_ctx* ctx, const pcdhip_bases* powers_of_g, const pc
   if (rc) (void)hipDeviceSynchronize();  // (an error partway: nothing of this call stays in flight on the side streams, or reads the frames above)
   return rc;
   });
+}
+
+int pcdhip_kzg_commit_last_plan(pcdhip_ctx* ctx, uint64_t out[4]) {
+  if (!ctx || !out) return PCDHIP_E_ARG;
+  for (int i = 0; i < 4; i++) out[i] = ctx->kzg_commit_plan[i];
+  return PCDHIP_OK;
 }
 
 // Both sides of the check are MSMs over one small uploaded vector (C_1..C_n, W_1..W_n, -g, -gamma_g): the left with the scalars

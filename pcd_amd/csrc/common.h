@@ -87,8 +87,13 @@ struct pcdhip_ctx {
   hipStream_t stream;
   pcd::MsmWorkspace msm_ws;
   pcd::MsmWorkspace aux_ws;  // fft ping-pong, witness-map vectors, groth16 scratch
-  pcd::MsmWorkspace short_ws;  // pcdhip_msm_short: scalars, plane partials, result (slots SHORT_*, capi_msm_short.hip)
+  pcd::MsmWorkspace short_ws;  // pcdhip_msm_short[_batch]: scalars, plane partials, result, the batch's scratch (slots SHORT_*, capi_msm_short.hip)
   size_t msm_short_max = 0;    // pcdhip_msm_set_short: the MSMs of pcdhip_kzg_open / _check over at most this many pairs skip the buckets (0: never)
+  // batched short MSMs (msm_short_batch_async): the host image of the last call's descriptor table -- it stays here until the next call,
+  // so the staging copy never reads a frame that has returned
+  std::vector<uint32_t> short_batch_table;
+  // pcdhip_kzg_commit_last_plan: large MSMs, hiding MSMs in the batch, hiding MSMs one at a time, launches of the batch chain
+  uint64_t kzg_commit_plan[4] = {0, 0, 0, 0};
   // the MSMs of a Groth16 proof run concurrently, each on its own stream with its own workspace: the
   // latency-bound bucket-reduction tail of one overlaps the throughput-bound accumulation of the others.
   // Streams 0 and 1 are created with the highest priority, 2 with the default one, 3..5 with the lowest.
@@ -148,6 +153,8 @@ struct pcdhip_ctx {
 
 namespace pcd {
 
+struct MsmShortBatchIn;  // one MSM of a batched short-MSM call (msm_short.hip.h)
+
 // ---- per-group entries (inst_group.hip, one object per group) ------------------------------------
 typedef hipError_t (*MsmFn)(MsmWorkspace&, hipStream_t, const MsmBasesView& bases, const uint32_t* scalars, uint32_t n,
                             uint32_t* out_dev, int c, uint32_t chunk, int sort_mode, MsmTimings* tm, MsmSharedSort* share,
@@ -186,6 +193,14 @@ struct GroupEntry {
   // Jacobian point in the device image
   size_t (*msm_short_scratch_words)(const MsmBasesView& bases, uint32_t n);
   hipError_t (*msm_short)(hipStream_t, const MsmBasesView& bases, const uint32_t* scalars, uint32_t n, uint32_t* scratch, uint32_t* out_dev);
+  // k independent short MSMs over one vector in one chain of at most three launches (msm_short.hip.h, "the batched form").  bases: the view
+  // at offset 0, every item names its own range.  scratch: msm_short_batch_scratch_words(bases, items, k) u32 words; the call stages its
+  // descriptor table there from *table_host by one copy on the stream.  scratch[0] is the call's error word afterwards, scratch[1 + j] that
+  // of the j-th item with n > 0.  Item j's Jacobian point (device image) goes to out_dev + out_slot_j * out_stride_words; the slot of
+  // an item with n == 0 is NOT written (the caller has zeroed it: Z = 0).  *launches = kernels launched (0, 2 or 3)
+  size_t (*msm_short_batch_scratch_words)(const MsmBasesView& bases, const MsmShortBatchIn* items, uint32_t k);
+  hipError_t (*msm_short_batch)(hipStream_t, const MsmBasesView& bases, const MsmShortBatchIn* items, uint32_t k, uint32_t* scratch,
+                                std::vector<uint32_t>* table_host, uint32_t* out_dev, size_t out_stride_words, uint32_t* launches);
   void (*identity_abi)(uint32_t* out_abi);  // the identity (0 : 1 : 0) as a Jacobian point in the C-ABI image (host)
 };
 const GroupEntry& group_entry(int curve_id, int group_id);  // group_id 1 / 2

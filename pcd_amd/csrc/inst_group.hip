@@ -90,6 +90,13 @@ size_t msm_short_scratch_words_entry(const MsmBasesView& bases, uint32_t n) { re
 hipError_t msm_short_entry(hipStream_t st, const MsmBasesView& bases, const uint32_t* scalars, uint32_t n, uint32_t* scratch, uint32_t* out_dev) {
   return msm_short_run<GT>(st, bases, scalars, n, scratch, out_dev);
 }
+size_t msm_short_batch_scratch_words_entry(const MsmBasesView& bases, const MsmShortBatchIn* items, uint32_t k) {
+  return msm_short_batch_plan<GT>(bases, items, k).scratch_words;
+}
+hipError_t msm_short_batch_entry(hipStream_t st, const MsmBasesView& bases, const MsmShortBatchIn* items, uint32_t k, uint32_t* scratch,
+                                 std::vector<uint32_t>* table_host, uint32_t* out_dev, size_t out_stride_words, uint32_t* launches) {
+  return msm_short_batch_run<GT>(st, bases, items, k, scratch, table_host, out_dev, out_stride_words, launches);
+}
 void identity_abi_entry(uint32_t* out_abi) { Jac<F>::infinity().to_abi(out_abi); }
 hipError_t precompute_entry(hipStream_t st, uint32_t* pts, uint32_t n, int groups, int shift) {
   return msm_precompute<GT>(st, pts, n, groups, shift);
@@ -137,7 +144,8 @@ hipError_t fb_inputs_entry(hipStream_t st, const uint32_t* tables, const uint32_
 const GroupEntry* PCD_CAT(pcd_group_entry_, PCD_GROUP_IDX)() {
   static const GroupEntry e = {Aff<F>::WORDS, MsmBaseStride<GT>::value, Aff<F>::ABI_WORDS, GT::FR::N32, GT::FR::BITS, msm_entry, precompute_entry,
                                points_in_entry, jac_out_entry, points_sum_entry, jac_sum_parts_entry, to_affine_entry, FB_TABLE_WORDS, fixed_base_entry,
-                               fb_tables_entry, fb_inputs_entry, msm_short_scratch_words_entry, msm_short_entry, identity_abi_entry};
+                               fb_tables_entry, fb_inputs_entry, msm_short_scratch_words_entry, msm_short_entry, msm_short_batch_scratch_words_entry,
+                               msm_short_batch_entry, identity_abi_entry};
   return &e;
 }
 

@@ -30,6 +30,9 @@ pub struct pcdhip_kzg_commit_item {
     pub poly: *const pcdhip_buf, pub len: u64, pub blinding: *const pcdhip_buf, pub blinding_len: u64,
     pub shifted_blinding: *const pcdhip_buf, pub shifted_blinding_len: u64, pub shifted_offset: u64, pub shifted: u32, pub _pad: u32,
 }
+/// one MSM of `pcdhip_msm_short_batch` / `_dev`: `n` pairs from point `base_offset` and scalar `scalar_offset` on
+#[repr(C)]
+pub struct pcdhip_msm_short_item { pub base_offset: u64, pub scalar_offset: u64, pub n: u64 }
 
 extern "C" {
     pub fn pcdhip_strerror(code: c_int) -> *const c_char;
@@ -50,6 +53,10 @@ extern "C" {
     pub fn pcdhip_msm_short(ctx: *mut pcdhip_ctx, bases: *const pcdhip_bases, offset: usize, scalars: *const u64, n: usize, out_xyz: *mut u64) -> c_int;
     pub fn pcdhip_msm_short_dev(ctx: *mut pcdhip_ctx, bases: *const pcdhip_bases, offset: usize, scalars: *const pcdhip_buf, scalar_offset: usize, n: usize,
                                 out_xyz: *mut u64) -> c_int;
+    pub fn pcdhip_msm_short_batch(ctx: *mut pcdhip_ctx, bases: *const pcdhip_bases, scalars: *const u64, scalars_n: usize,
+                                  items: *const pcdhip_msm_short_item, k: usize, out_xyz: *mut u64) -> c_int;
+    pub fn pcdhip_msm_short_batch_dev(ctx: *mut pcdhip_ctx, bases: *const pcdhip_bases, scalars: *const pcdhip_buf,
+                                      items: *const pcdhip_msm_short_item, k: usize, out_xyz: *mut u64) -> c_int;
     pub fn pcdhip_msm_set_short(ctx: *mut pcdhip_ctx, max_n: usize) -> c_int;
     pub fn pcdhip_to_affine(ctx: *mut pcdhip_ctx, curve: c_int, group: c_int, xyz: *const u64, n: usize, out_xy: *mut u64, out_inf: *mut u8) -> c_int;
     // K2: Radix2EvaluationDomain / GeneralEvaluationDomain transforms
@@ -90,6 +97,7 @@ extern "C" {
     pub fn pcdhip_kzg_commit(ctx: *mut pcdhip_ctx, powers_of_g: *const pcdhip_bases, powers_of_gamma_g: *const pcdhip_bases,
                              shifted_powers_of_g: *const pcdhip_bases, items: *const pcdhip_kzg_commit_item, k: usize, comm_xy: *mut u64,
                              comm_inf: *mut u8, shifted_xy: *mut u64, shifted_inf: *mut u8, trimmed_len: *mut u64) -> c_int;
+    pub fn pcdhip_kzg_commit_last_plan(ctx: *mut pcdhip_ctx, out: *mut u64) -> c_int;
 }
 
 /// `PCDHIP_E_*` (include/pcdhip.h)

@@ -16,7 +16,21 @@ bound.  MNT4-298 at n = 2^20 and MNT4-753 at n = 2^18 by default.  Median of REP
                         parts of (a) apart.  Device events.
   *_short_ms            (a), the bound and the hiding MSMs again after pcdhip_msm_set_short(ctx, 8): the 2-coefficient hiding MSMs skip the buckets.
 
-    python tools/kzg_commit_round_bench.py [--cases 0:20,2:18] [--reps 7] [--out profiles/kzg_commit_bench.json]"""
+    python tools/kzg_commit_round_bench.py [--cases 0:20,2:18] [--reps 7] [--out profiles/kzg_commit_bench.json]
+
+--batch measures the batched hiding MSMs instead (device events; median, min and max of REPS after one warm-up), per curve:
+  commit_not_hiding     the round without blinding polynomials: what the hiding round should approach;
+  commit_default        the hiding round under pcdhip_msm_set_short(ctx, 0): eleven bucket pipelines in sequence;
+  commit_short8_gamma4 / _gamma64
+                        the hiding round under pcdhip_msm_set_short(ctx, 8) with a 4-point powers_of_gamma_g (no copies: a short chain is the
+                        scalar's bits) and a 64-point one (the smallest upload that gets window copies: the chain is about 2c) -- the
+                        eleven hiding MSMs as ONE batched chain where the library has it, eleven chains in sequence where it has not;
+  short_two_pairs_gamma4 / _gamma64
+                        one pcdhip_msm_short_dev of two pairs over each handle, alone;
+  batch22_gamma4 / _gamma64
+                        22 such MSMs through pcdhip_msm_short_batch_dev (libraries that have it): about one of the above by count, not 22.
+
+    python tools/kzg_commit_round_bench.py --batch [--cases 0:20,2:18] [--reps 7] [--out profiles/kzg_commit_bench_batch.json]"""
 import argparse
 import json
 import os
@@ -132,8 +146,78 @@ def bench_curve(ctx, curve, log_n, reps):
     return res
 
 
+def spread_of(fn, reps):
+    fn()
+    ts = [fn() for _ in range(reps)]
+    return {"median_ms": round(statistics.median(ts), 3), "min_ms": round(min(ts), 3), "max_ms": round(max(ts), 3)}
+
+
+def bench_batch(ctx, curve, log_n, reps):
+    fr = co.CURVE_FR[curve]
+    n = 1 << log_n
+    npow = 3 * n // 2
+    lens = [n, n, n, npow] + [n // 2] * 5
+    shifted = {1: npow - n, 4: 7}  # item -> shifted_offset
+    pts = co.gen_points_mt(curve, 1, npow, seed=161, threads=16)
+    bases = ctx.bases_upload(curve, 1, pts)
+    sbases = ctx.bases_upload(curve, 1, pts[::-1].copy())
+    del pts
+    gpts = co.gen_points(curve, 1, 64, seed=162)
+    gammas = {4: ctx.bases_upload(curve, 1, gpts[:4]), 64: ctx.bases_upload(curve, 1, gpts)}
+    polys = [ctx.buf_upload(fr, co.gen_field(fr, m, seed=170 + j)) for j, m in enumerate(lens)]
+    bl_mont = [co.gen_field(fr, 2, seed=190 + j) for j in range(len(lens))]
+    bls = [ctx.buf_upload(fr, x) for x in bl_mont]
+    hiding = [dict(poly=p, blinding=bls[j], shifted=j in shifted, shifted_offset=shifted.get(j, 0),
+                   shifted_blinding=bls[j] if j in shifted else None) for j, p in enumerate(polys)]
+    bare = [dict(poly=p, shifted=j in shifted, shifted_offset=shifted.get(j, 0)) for j, p in enumerate(polys)]
+    has_batch = hasattr(ctx, "msm_short_batch")
+    res = {"curve": co.CURVE_NAMES[curve], "n": n, "powers": npow, "lens": lens, "shifted_items": sorted(shifted), "hiding_msms": 11,
+           "library_has_batch": has_batch}
+    out = {}
+
+    def commit(items, g, tag=None):
+        ctx.timer_start()
+        r = ctx.kzg_commit(bases, items, powers_of_gamma_g=gammas[g], shifted_powers=sbases)
+        ms = ctx.timer_stop()
+        if tag:
+            out[tag] = r
+        return ms
+
+    def timed(fn):
+        ctx.timer_start()
+        fn()
+        return ctx.timer_stop()
+
+    res["commit_not_hiding"] = spread_of(lambda: commit(bare, 4), reps)
+    res["commit_default"] = spread_of(lambda: commit(hiding, 4, "default4"), reps)
+    commit(hiding, 64, "default64")
+    ctx.msm_set_short(8)
+    try:
+        for g in (4, 64):
+            res[f"commit_short8_gamma{g}"] = spread_of(lambda: commit(hiding, g, f"short{g}"), reps)
+            if has_batch:
+                res[f"commit_short8_gamma{g}_plan"] = list(ctx.kzg_commit_last_plan())
+            res[f"short8_gamma{g}_agrees"] = bool(all(np.array_equal(a, b) for a, b in zip(out[f"default{g}"], out[f"short{g}"])))
+    finally:
+        ctx.msm_set_short(0)
+    # the standalone short MSM of two pairs, and 22 of them as one batch: scalars = the 9 blinding polynomials, canonical, back to back
+    canon = ctx.buf_upload(fr, np.concatenate([co.fp_op(fr, "to_canonical", x) for x in bl_mont]))
+    items22 = [(0, 2 * (j % len(lens)), 2) for j in range(22)]
+    for g in (4, 64):
+        res[f"short_two_pairs_gamma{g}"] = spread_of(lambda: timed(lambda: ctx.msm_short(gammas[g], canon, n=2)), reps)
+        if has_batch:
+            res[f"batch22_gamma{g}"] = spread_of(lambda: timed(lambda: ctx.msm_short_batch(gammas[g], canon, items22)), reps)
+            one = co.to_affine(curve, 1, ctx.msm_short(gammas[g], canon, n=2, scalar_offset=2))
+            got = co.to_affine(curve, 1, ctx.msm_short_batch(gammas[g], canon, items22)[1])
+            res[f"batch22_gamma{g}_agrees"] = bool(np.array_equal(one[0], got[0]))
+    for x in polys + bls + [canon, bases, sbases] + list(gammas.values()):
+        x.free()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", action="store_true", help="the batched hiding MSMs (see above) instead of the round's three paths")
     ap.add_argument("--cases", default="0:20,2:18", help="curve:log_n, comma separated")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None)
@@ -142,10 +226,10 @@ def main():
     results = []
     for case in a.cases.split(","):
         c, l = case.split(":")
-        results.append(bench_curve(ctx, int(c), int(l), a.reps))
+        results.append((bench_batch if a.batch else bench_curve)(ctx, int(c), int(l), a.reps))
         print(json.dumps(results[-1]), flush=True)
     ctx.close()
-    line = json.dumps({"tool": "kzg_commit_round_bench", "reps": a.reps, "results": results})
+    line = json.dumps({"tool": "kzg_commit_round_bench", "mode": "batch" if a.batch else "round", "reps": a.reps, "results": results})
     print(line)
     if a.out:
         with open(a.out, "w") as f:
