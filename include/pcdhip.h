@@ -549,6 +549,57 @@ int pcdhip_poly_div_vanishing(pcdhip_ctx* ctx, const pcdhip_buf* p, size_t len, 
  * pcdhip_domain_size(field, la + lb - 1); PCDHIP_E_SIZE_UNSUPPORTED when that is 0.  out may be a or b. */
 int pcdhip_poly_mul(pcdhip_ctx* ctx, const pcdhip_buf* a, size_t la, const pcdhip_buf* b, size_t lb, pcdhip_buf* out, size_t* out_len);
 
+/* ---- K9 Marlin's AHP rounds 2 and 3: r(alpha, .), t(X) and the rational sumcheck -----------------------------------------------
+ * What ark-marlin's prover computes between its first commitments and its openings, besides the transforms, K8 and the commitments:
+ * on device vectors of ABI Montgomery elements of ONE field, on the context's own stream and workspaces (a multi-device context
+ * addresses its device 0).  Null pointers, a count beyond a buffer's n and mixed fields give PCDHIP_E_ARG.  These calls only QUEUE
+ * their launches: none waits for the device (pcdhip_buf_download, pcdhip_sync and every K7 / K8 call do), and nothing of size n or nnz
+ * is computed on the host per call.  Field elements of the host (x, eta, alpha, beta, the coefficients) are ABI Montgomery limbs. */
+/* ark-marlin `batch_eval_unnormalized_bivariate_lagrange_poly_with_diff_inputs`: out_i = (x^domain_n - 1) / (x - w^i) for i < domain_n,
+ * w the generator the resident transform of that size uses (radix-2 or mixed-radix).  domain_n must be a domain size
+ * (pcdhip_domain_size(field_id, domain_n) == domain_n), PCDHIP_E_SIZE_UNSUPPORTED otherwise.  When x lies in the domain EVERY output is
+ * 0, as upstream's formula gives it: the batch inversion leaves the zero difference in place, and the scale x^domain_n - 1 is 0.
+ * Two launches: the differences, then the batch inversion of pcdhip_vec_batch_inverse with that scale. */
+int pcdhip_domain_bivariate_lagrange(pcdhip_ctx* ctx, int field_id, size_t domain_n, const uint64_t* x_mont, pcdhip_buf* out);
+/* The three constraint matrices of an index, resident for t(X): transposed on the host (an index permutation) with the variables at
+ * their places in H, pi = ark-marlin's `reindex_by_subdomain`: period = domain_h_n / domain_x_n, pi(c) = c period for c < domain_x_n,
+ * else i = c - domain_x_n and pi(c) = i + i / (period - 1) + 1.  PCDHIP_E_ARG unless domain_x_n divides domain_h_n, both are domain
+ * sizes, the matrices have the same number of rows, num_rows <= domain_h_n, num_cols <= domain_h_n and every column index is below
+ * num_cols.  Duplicate (row, column) entries accumulate; explicit zeros are allowed.  A transposed row of more than 16 entries is cut
+ * into segments of at most S = 4096 entries (the environment's PCDHIP_MARLIN_SEG at upload, 64 .. 2^20: a tuning knob), one wave each. */
+typedef struct pcdhip_marlin_mats pcdhip_marlin_mats;
+int pcdhip_marlin_mats_upload(pcdhip_ctx* ctx, int field_id, const pcdhip_csr* A, const pcdhip_csr* B, const pcdhip_csr* C, size_t num_cols,
+                              size_t domain_h_n, size_t domain_x_n, pcdhip_marlin_mats** out);
+void pcdhip_marlin_mats_free(pcdhip_ctx* ctx, pcdhip_marlin_mats* mats);
+/* out[0] = the segment length S of this handle, out[1] = segments (= waves of the second launch), out[2] = outputs that own segments,
+ * out[3] = launches of one pcdhip_marlin_t_evals (1, or 3 with segments) */
+int pcdhip_marlin_mats_info(const pcdhip_marlin_mats* mats, uint64_t out[4]);
+/* ark-marlin `calculate_t` on H: t_out[j] = sum_M eta_M sum_{(r, c, v) in M, pi(c) = j} v r_alpha[r] for j < domain_h_n, M = A, B, C
+ * (eta_mont: 3 elements; r_alpha: at least num_rows elements, e.g. from pcdhip_domain_bivariate_lagrange; t_out: at least domain_h_n,
+ * not r_alpha).  One lane per output walks its short rows in the three matrices and applies eta_M once per row sum; the segments of
+ * the long rows get a wave each and a small third launch adds them in: no atomics, at most three launches. */
+int pcdhip_marlin_t_evals(pcdhip_ctx* ctx, const pcdhip_marlin_mats* mats, const uint64_t* eta_mont /* 3 elements */,
+                          const pcdhip_buf* r_alpha, pcdhip_buf* t_out);
+/* The rational sumcheck of round 3 over the index's row / col / row_col / val evaluations (on K, and again on the larger domain B),
+ * for i < n and M = A, B, C:
+ *   d_M = alpha beta - alpha row_M[i] - beta col_M[i] + row_col_M[i]   -- row_col taken as given (on B it is NOT the pointwise product);
+ *   d_M = (beta - row_M[i]) (alpha - col_M[i])                         -- when row_col, or each of its entries, is NULL;
+ *   b_i = d_A d_B d_C      a_i = c_A val_A[i] d_B d_C + c_B val_B[i] d_A d_C + c_C val_C[i] d_A d_B       (coeff_mont = c_A, c_B, c_C)
+ * in ONE launch, one lane per element.  a_out and b_out must not be each other nor any input (PCDHIP_E_ARG); n == 0 succeeds without a
+ * launch. */
+int pcdhip_marlin_sumcheck_ab(pcdhip_ctx* ctx, const uint64_t* alpha_mont, const uint64_t* beta_mont, const uint64_t* coeff_mont /* 3 */,
+                              const pcdhip_buf* const row[3], const pcdhip_buf* const col[3],
+                              const pcdhip_buf* const row_col[3] /* array or entries nullable */, const pcdhip_buf* const val[3], size_t n,
+                              pcdhip_buf* a_out, pcdhip_buf* b_out);
+/* f_i = a_i / b_i, and f_i = 0 where b_i = 0: that kernel into workspace, the batch inversion of b, the pointwise product (three
+ * launches); f_out must not be an input.  Upstream inverts per matrix (f = sum_M c_M val_M / d_M), so where one d_M is zero it drops
+ * that matrix's term only, while this call gives 0; the two agree whenever alpha and beta lie outside H, which is how the verifier
+ * samples them. */
+int pcdhip_marlin_sumcheck_f(pcdhip_ctx* ctx, const uint64_t* alpha_mont, const uint64_t* beta_mont, const uint64_t* coeff_mont /* 3 */,
+                             const pcdhip_buf* const row[3], const pcdhip_buf* const col[3],
+                             const pcdhip_buf* const row_col[3] /* array or entries nullable */, const pcdhip_buf* const val[3], size_t n,
+                             pcdhip_buf* f_out);
+
 /* ---- timing helpers (HIP events on the context's stream, for bench.py) ------------------------- */
 int pcdhip_timer_start(pcdhip_ctx* ctx);
 int pcdhip_timer_stop(pcdhip_ctx* ctx, float* out_ms);

@@ -77,6 +77,8 @@ EXPORTS = [
     "pcdhip_vec_mul", "pcdhip_vec_batch_inverse", "pcdhip_poly_div_vanishing", "pcdhip_poly_mul",
     "pcdhip_msm_short", "pcdhip_msm_short_dev", "pcdhip_msm_set_short",
     "pcdhip_msm_short_batch", "pcdhip_msm_short_batch_dev", "pcdhip_kzg_commit_last_plan",
+    "pcdhip_domain_bivariate_lagrange", "pcdhip_marlin_mats_upload", "pcdhip_marlin_mats_free", "pcdhip_marlin_mats_info", "pcdhip_marlin_t_evals",
+    "pcdhip_marlin_sumcheck_ab", "pcdhip_marlin_sumcheck_f",
 ]
 
 
@@ -94,7 +96,7 @@ def lib():
         _LIB.pcdhip_domain_size.restype = C.c_size_t
         for name in ("pcdhip_serialized_size", "pcdhip_proof_serialized_size", "pcdhip_vk_serialized_size"):
             getattr(_LIB, name).restype = C.c_size_t
-        for name in ("pcdhip_buf_free", "pcdhip_bases_free", "pcdhip_g16_pk_free", "pcdhip_host_free", "pcdhip_pvk_free"):
+        for name in ("pcdhip_buf_free", "pcdhip_bases_free", "pcdhip_g16_pk_free", "pcdhip_host_free", "pcdhip_pvk_free", "pcdhip_marlin_mats_free"):
             getattr(_LIB, name).restype = None
         vp, sz, szp = C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)
         _LIB.pcdhip_vec_mul.argtypes = [vp, vp, vp, sz, vp]
@@ -104,6 +106,13 @@ def lib():
         _LIB.pcdhip_kzg_commit.argtypes = [vp, vp, vp, vp, C.POINTER(KzgCommitItem), sz, vp, vp, vp, vp, vp]
         _LIB.pcdhip_msm_short_batch.argtypes = [vp, vp, vp, sz, C.POINTER(MsmShortItem), sz, vp]
         _LIB.pcdhip_msm_short_batch_dev.argtypes = [vp, vp, vp, C.POINTER(MsmShortItem), sz, vp]
+        _LIB.pcdhip_domain_bivariate_lagrange.argtypes = [vp, C.c_int, sz, vp, vp]
+        _LIB.pcdhip_marlin_mats_upload.argtypes = [vp, C.c_int, vp, vp, vp, sz, sz, sz, vp]
+        _LIB.pcdhip_marlin_mats_free.argtypes = [vp, vp]
+        _LIB.pcdhip_marlin_mats_info.argtypes = [vp, vp]
+        _LIB.pcdhip_marlin_t_evals.argtypes = [vp, vp, vp, vp, vp]
+        _LIB.pcdhip_marlin_sumcheck_ab.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
+        _LIB.pcdhip_marlin_sumcheck_f.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     return _LIB
 
 
@@ -676,6 +685,68 @@ class Context:
         self._call_into(own, lambda: lib().pcdhip_poly_mul(self._ctx, a._h, la, b._h, lb, out._h, C.byref(n)))
         return out, n.value
 
+    # ---- K9: Marlin's AHP rounds 2 and 3
+    def domain_bivariate_lagrange(self, field, domain_n, x_mont, out=None):
+        """out_i = (x^domain_n - 1) / (x - w^i) over the domain of domain_n elements (all zero when x lies in it) -> out"""
+        domain_n = int(domain_n)
+        own = [] if out is not None else [self.buf_alloc(field, domain_n)]
+        out = out if out is not None else own[0]
+        self._call_into(own, lambda: lib().pcdhip_domain_bivariate_lagrange(self._ctx, field, domain_n, _p(_u64(x_mont)), out._h))
+        return out
+
+    def marlin_mats_upload(self, field, r1cs, domain_h_n, domain_x_n, num_cols=None):
+        """the constraint matrices of `r1cs` (rp_/col_/coeff_{a,b,c}, num_vars) resident for marlin_t_evals: transposed, the variables at
+        reindex_by_subdomain's places in H"""
+        A = self._csr(r1cs.rp_a, r1cs.col_a, r1cs.coeff_a)
+        B = self._csr(r1cs.rp_b, r1cs.col_b, r1cs.coeff_b)
+        Cm = self._csr(r1cs.rp_c, r1cs.col_c, r1cs.coeff_c)
+        num_cols = r1cs.num_vars if num_cols is None else int(num_cols)
+        h = C.c_void_p()
+        self._check(lib().pcdhip_marlin_mats_upload(self._ctx, field, C.byref(A), C.byref(B), C.byref(Cm), num_cols, int(domain_h_n),
+                                                    int(domain_x_n), C.byref(h)))
+        return MarlinMats(self, h, field, int(domain_h_n))
+
+    def marlin_t_evals(self, mats, eta_mont, r_alpha, out=None):
+        """t_out[j] = sum_M eta_M sum_{(r, c, v) in M, pi(c) = j} v r_alpha[r] for j < |H| -> out"""
+        own = [] if out is not None else [self.buf_alloc(mats.field, mats.domain_h_n)]
+        out = out if out is not None else own[0]
+        eta = _u64(eta_mont).reshape(3, FIELD_LIMBS[mats.field])
+        self._call_into(own, lambda: lib().pcdhip_marlin_t_evals(self._ctx, mats._h, _p(eta), r_alpha._h, out._h))
+        return out
+
+    @staticmethod
+    def _three(bufs):
+        if bufs is None:
+            return None
+        return (C.c_void_p * 3)(*[b._h.value if b is not None else None for b in bufs])
+
+    def marlin_sumcheck_ab(self, alpha_mont, beta_mont, coeff_mont, row, col, row_col, val, n=None, a_out=None, b_out=None):
+        """the rational sumcheck's a and b over the three matrices' row / col / row_col (None: the product form) / val vectors -> (a, b)"""
+        n = min(x.n for x in list(row) + list(col) + list(val)) if n is None else int(n)
+        f = row[0].field
+        own = []
+        for o in (a_out, b_out):
+            if o is None:
+                own.append(self.buf_alloc(f, n))
+        a_out = a_out if a_out is not None else own[0]
+        b_out = b_out if b_out is not None else own[-1]
+        cf = _u64(coeff_mont).reshape(3, FIELD_LIMBS[f])
+        self._call_into(own, lambda: lib().pcdhip_marlin_sumcheck_ab(self._ctx, _p(_u64(alpha_mont)), _p(_u64(beta_mont)), _p(cf), self._three(row),
+                                                                     self._three(col), self._three(row_col), self._three(val), n, a_out._h,
+                                                                     b_out._h))
+        return a_out, b_out
+
+    def marlin_sumcheck_f(self, alpha_mont, beta_mont, coeff_mont, row, col, row_col, val, n=None, out=None):
+        """f_i = a_i / b_i of marlin_sumcheck_ab, 0 where b_i = 0 -> out"""
+        n = min(x.n for x in list(row) + list(col) + list(val)) if n is None else int(n)
+        f = row[0].field
+        own = [] if out is not None else [self.buf_alloc(f, n)]
+        out = out if out is not None else own[0]
+        cf = _u64(coeff_mont).reshape(3, FIELD_LIMBS[f])
+        self._call_into(own, lambda: lib().pcdhip_marlin_sumcheck_f(self._ctx, _p(_u64(alpha_mont)), _p(_u64(beta_mont)), _p(cf), self._three(row),
+                                                                    self._three(col), self._three(row_col), self._three(val), n, out._h))
+        return out
+
     def kzg_open(self, powers_of_g, p, z_mont, length=None, powers_of_gamma_g=None, blinding=None, blinding_len=None):
         """KZG10::open -> (w Jacobian X||Y||Z, p(z), blinding(z) or None when there is no blinding polynomial)"""
         length = p.n if length is None else int(length)
@@ -842,6 +913,22 @@ class DeviceBuf:
     def free(self):
         if self._h:
             lib().pcdhip_buf_free(self.ctx._ctx, self._h)
+            self._h = None
+
+
+class MarlinMats:
+    def __init__(self, ctx, h, field, domain_h_n):
+        self.ctx, self._h, self.field, self.domain_h_n = ctx, h, field, domain_h_n
+
+    def info(self):
+        """{"seg_len", "segments", "long_outputs", "launches"} of this handle (pcdhip_marlin_mats_info)"""
+        out = (C.c_uint64 * 4)()
+        self.ctx._check(lib().pcdhip_marlin_mats_info(self._h, out))
+        return dict(zip(["seg_len", "segments", "long_outputs", "launches"], [int(v) for v in out]))
+
+    def free(self):
+        if self._h:
+            lib().pcdhip_marlin_mats_free(self.ctx._ctx, self._h)
             self._h = None
 
 

@@ -106,6 +106,15 @@ int witness_finish_dev(pcdhip_ctx* ctx, int field_id, const Dom& d, const uint32
 int witness_map_dev(pcdhip_ctx* ctx, int field_id, const DevCsr mats[3], const uint32_t* z_dev, size_t num_inputs, Dom* dom_out,
                     hipEvent_t after_spmv = nullptr);
 
+// ---- capi_setup.hip
+struct HostCsrT {
+  std::vector<uint64_t> rp;
+  std::vector<uint32_t> col;
+  std::vector<uint64_t> coeff;
+  pcdhip_csr view;
+};
+int transpose_csr(const pcdhip_csr* m, size_t cols, size_t limbs, HostCsrT* t, const uint32_t* perm = nullptr, size_t rows_out = 0);
+
 // ---- capi_verify.hip
 void negate_point(int curve_id, int group_id, uint64_t* xy);
 void scalar_lincomb(int fr, const uint64_t* const* a, const uint64_t* const* b, size_t n, uint64_t* out);

@@ -18,36 +18,36 @@ int fixed_base_dev(pcdhip_ctx* ctx, const GroupEntry& ge, const uint32_t* base_a
   return PCDHIP_OK;
 }
 
-// transpose of a CSR matrix with `cols` columns, as CSR (host side: an index permutation, no field arithmetic)
-struct HostCsrT {
-  std::vector<uint64_t> rp;
-  std::vector<uint32_t> col;
-  std::vector<uint64_t> coeff;
-  pcdhip_csr view;
-};
-int transpose_csr(const pcdhip_csr* m, size_t cols, size_t limbs, HostCsrT* t) {
+}  // namespace
+
+namespace pcd {
+// transpose of a CSR matrix with `cols` columns, as CSR (host side: an index permutation, no field arithmetic).  With `perm`, column c
+// becomes row perm[c] of a result with `rows_out` rows (every perm[c] < rows_out; the rows that no column maps to stay empty)
+int transpose_csr(const pcdhip_csr* m, size_t cols, size_t limbs, HostCsrT* t, const uint32_t* perm, size_t rows_out) {
   if (!m || !m->row_ptr) return PCDHIP_E_ARG;
   const uint64_t nnz = m->row_ptr[m->num_rows];
   if (nnz && (!m->col || !m->coeff)) return PCDHIP_E_ARG;
-  t->rp.assign(cols + 1, 0);
+  const size_t rows = perm ? rows_out : cols;
+  auto at = [&](uint32_t c) -> size_t { return perm ? perm[c] : c; };
+  t->rp.assign(rows + 1, 0);
   for (uint64_t k = 0; k < nnz; k++) {
-    if (m->col[k] >= cols) return PCDHIP_E_ARG;
-    t->rp[m->col[k] + 1]++;
+    if (m->col[k] >= cols || at(m->col[k]) >= rows) return PCDHIP_E_ARG;
+    t->rp[at(m->col[k]) + 1]++;
   }
-  for (size_t c = 0; c < cols; c++) t->rp[c + 1] += t->rp[c];
+  for (size_t c = 0; c < rows; c++) t->rp[c + 1] += t->rp[c];
   t->col.resize(nnz);
   t->coeff.resize(nnz * limbs);
   std::vector<uint64_t> fill(t->rp.begin(), t->rp.end() - 1);
   for (uint64_t r = 0; r < m->num_rows; r++)
     for (uint64_t k = m->row_ptr[r]; k < m->row_ptr[r + 1]; k++) {
-      const uint64_t d = fill[m->col[k]]++;
+      const uint64_t d = fill[at(m->col[k])]++;
       t->col[d] = (uint32_t)r;
       memcpy(&t->coeff[d * limbs], m->coeff + k * limbs, limbs * 8);
     }
-  t->view = {cols, t->rp.data(), t->col.data(), t->coeff.data()};
+  t->view = {rows, t->rp.data(), t->col.data(), t->coeff.data()};
   return PCDHIP_OK;
 }
-}  // namespace
+}  // namespace pcd
 
 extern "C" {
 

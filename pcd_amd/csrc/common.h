@@ -57,6 +57,27 @@ struct DevCsr {
   const uint32_t* nl = nullptr; const int8_t* lc = nullptr; const uint32_t* long_rows = nullptr; uint32_t n_long = 0;
 };
 }
+namespace pcd {
+// K9 (pcdhip_marlin_t_evals): the three constraint matrices TRANSPOSED, their rows already at reindex_by_subdomain's places: row j of m[M]
+// lists the (constraint r, coefficient) entries of the variable with pi(c) = j.  A lane serves the rows of up to SPMV_LONG_ROW entries; a
+// longer row is cut into segments of at most `seg_len` entries, one wave each, listed in `segs` by (row, matrix); `long_out` names the
+// distinct rows that own segments and `long_seg_lo` (n_long_out + 1 entries) where the segments of each begin.
+constexpr uint32_t MARLIN_T_SEG = 4096;
+struct MarlinSeg { uint32_t mat, row; uint64_t lo, hi; };
+struct MarlinMatsDev {
+  DevCsr m[3];
+  uint32_t rows = 0;  // |H|
+  const MarlinSeg* segs = nullptr; uint32_t n_segs = 0;
+  const uint32_t* long_out = nullptr; const uint32_t* long_seg_lo = nullptr; uint32_t n_long_out = 0;
+};
+}
+struct pcdhip_marlin_mats {
+  int field_id = 0;
+  size_t domain_h_n = 0, domain_x_n = 0, num_rows = 0, num_cols = 0;
+  uint32_t seg_len = 0;
+  void* dev = nullptr;  // one block: the three matrices, then the segment tables
+  pcd::MarlinMatsDev view;
+};
 struct pcdhip_g16_pk {
   // constraint matrices kept resident by pcdhip_g16_pk_set_r1cs (fixed per circuit, like the key)
   void* r1cs_dev = nullptr;
@@ -268,6 +289,19 @@ struct FieldEntry {
   // trimmed_dev[j] = the index of polynomial j's highest non-zero coefficient below len_j, plus one (k words, ZEROED by the caller on the
   // stream before the launch; a zero or empty polynomial leaves 0)
   hipError_t (*poly_commit_scalars)(hipStream_t, const PolyCommitDesc* descs_dev, uint32_t k, uint64_t max_len, uint32_t* trimmed_dev);
+  // K9 (marlin.hip.h), C-ABI Montgomery vectors on the device, field elements of the host in C-ABI words.
+  // out_i = (x^n - 1) / (x - w^i), i < n: the differences, then the batch inversion of vec_batch_inverse in place with the scale
+  // x^n - 1.  domain_consts = FftTables::consts of the domain (w first), tw = its tw_len resident powers of w; both null for n == 1
+  hipError_t (*marlin_lagrange)(hipStream_t, const void* domain_consts, const uint32_t* tw, uint32_t tw_len, const uint32_t* x_abi,
+                                uint64_t n, uint32_t* out);
+  // t_out[j] = sum_M eta_M (row j of mats.m[M]) . r, j < mats.rows; part: mats.n_segs elements of scratch (device image); at most three
+  // launches, *launches (nullable) says how many
+  hipError_t (*marlin_t_evals)(hipStream_t, const MarlinMatsDev& mats, const uint32_t* eta_abi, const uint32_t* r, uint32_t* part,
+                               uint32_t* t_out, int* launches);
+  // the rational sumcheck's a and b (marlin.hip.h marlin_sumcheck_ab), one launch; rc[0] == null: d_M = (beta - row_M)(alpha - col_M)
+  hipError_t (*marlin_sumcheck_ab)(hipStream_t, const uint32_t* alpha_abi, const uint32_t* beta_abi, const uint32_t* coeff_abi,
+                                   const uint32_t* const row[3], const uint32_t* const col[3], const uint32_t* const rc[3],
+                                   const uint32_t* const val[3], uint64_t n, uint32_t* a_out, uint32_t* b_out);
 };
 const FieldEntry& field_entry(int field_id);
 

@@ -33,6 +33,15 @@ typedef FT FTP;
 #endif
 static_assert(sizeof(FTP) == sizeof(FT), "same image");
 
+#define PCD_CAT_(a, b) a##b
+#define PCD_CAT(a, b) PCD_CAT_(a, b)
+// inst_marlin.hip, the same field: the differences x - w^i (and the scale x^n - 1 in ABI words into vh_abi), the sumcheck's a and b
+hipError_t PCD_CAT(pcd_marlin_diffs_, PCD_FIELD_IDX)(hipStream_t, const void* domain_consts, const uint32_t* tw, uint32_t tw_len,
+                                                     const uint32_t* x_abi, uint64_t n, uint32_t* out, uint32_t* vh_abi);
+hipError_t PCD_CAT(pcd_marlin_sumcheck_ab_, PCD_FIELD_IDX)(hipStream_t, const uint32_t* alpha_abi, const uint32_t* beta_abi, const uint32_t* coeff_abi,
+                                                           const uint32_t* const row[3], const uint32_t* const col[3], const uint32_t* const rc[3],
+                                                           const uint32_t* const val[3], uint64_t n, uint32_t* a_out, uint32_t* b_out);
+
 namespace {
 
 constexpr int EW = FT::WORDS;
@@ -533,15 +542,104 @@ hipError_t poly_div_vanishing_run(hipStream_t st, const uint32_t* p, uint64_t le
   return hipGetLastError();
 }
 
+// ---- K9: r(alpha, .) on H and the rational sumcheck live in a unit of their own (inst_marlin.hip: their inlined 753-bit products
+// compile beside this object, not behind it); t(X) is here, next to the mat-vecs whose small-coefficient sums it shares.
+hipError_t marlin_lagrange_run(hipStream_t st, const void* domain_consts, const uint32_t* tw, uint32_t tw_len, const uint32_t* x_abi, uint64_t n,
+                               uint32_t* out) {
+  if (n == 0) return hipSuccess;
+  uint32_t vh[FT::ABI_WORDS];
+  PCD_HIP_TRY(PCD_CAT(pcd_marlin_diffs_, PCD_FIELD_IDX)(st, domain_consts, tw, tw_len, x_abi, n, out, vh));
+  return vec_batch_inverse_run(st, out, n, vh, out);
+}
+
+// t(X) on H: the transposed mat-vecs of the three matrices against r = r(alpha, .), read as it stands (ABI words: the scale R, on which
+// the sums stay -- light entries add c * r, heavy ones multiply r by a coefficient in the device image), eta_M applied once per row sum.
+struct MarlinEta { FT e[3]; };
+PCD_DEV FT marlin_eta_of(const MarlinEta& eta, uint32_t m) { return m == 0 ? eta.e[0] : m == 1 ? eta.e[1] : eta.e[2]; }
+// the entries [lo, hi) of a row whose light part ends at mid, every `step`-th from lo + first
+PCD_DEV FT marlin_row_sum(const DevCsr& m, const uint32_t* __restrict__ r, uint64_t lo, uint64_t mid, uint64_t hi, uint32_t first, uint32_t step) {
+  constexpr int AW = FT::ABI_WORDS;
+  FT acc = FT::zero();
+  SpmvLight L;
+  for (uint64_t k = lo + first; k < mid && k < hi; k += step) L.add((int)m.lc[k], FT::unpack32(r + (size_t)m.col[k] * AW), acc);
+  L.flush(acc);
+  const uint64_t h0 = lo > mid ? lo : mid;
+  for (uint64_t k = h0 + first; k < hi; k += step) acc = acc + FT::load(m.coeff + k * EW) * FT::unpack32(r + (size_t)m.col[k] * AW);
+  return acc;
+}
+// one lane per output j: its rows of up to SPMV_LONG_ROW entries in the three matrices; longer rows are left to the segments
+__global__ void __launch_bounds__(256) marlin_t_short_kernel(const MarlinMatsDev mm, const MarlinEta eta, const uint32_t* __restrict__ r,
+                                                             uint32_t* __restrict__ t_out) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= mm.rows) return;
+  FT acc = FT::zero();
+#pragma unroll 1
+  for (uint32_t M = 0; M < 3; M++) {
+    const DevCsr& m = mm.m[M];
+    const uint64_t lo = m.rp[j], hi = m.rp[j + 1];
+    if (hi == lo || hi - lo > SPMV_LONG_ROW) continue;
+    acc = acc + marlin_eta_of(eta, M) * marlin_row_sum(m, r, lo, lo + m.nl[j], hi, 0, 1);
+  }
+  acc.canonical().pack32(t_out + (size_t)j * FT::ABI_WORDS);
+}
+// one wave per segment of a long row: lanes stride over its entries, a butterfly of additions, the partial sum to part[segment]
+__global__ void __launch_bounds__(64) marlin_t_seg_kernel(const MarlinMatsDev mm, const uint32_t* __restrict__ r, uint32_t* __restrict__ part) {
+  const uint32_t s = blockIdx.x;
+  if (s >= mm.n_segs) return;
+  const MarlinSeg sg = mm.segs[s];
+  const DevCsr& m = mm.m[sg.mat];
+  FT acc = marlin_row_sum(m, r, sg.lo, m.rp[sg.row] + m.nl[sg.row], sg.hi, threadIdx.x, 64);
+  for (int d = 32; d > 0; d >>= 1) {
+    FT o;
+#pragma unroll
+    for (int q = 0; q < FT::N; q++) o.v[q] = (uint32_t)__shfl_xor((int)acc.v[q], d, 64);
+    acc = acc + o;
+  }
+  if (threadIdx.x == 0) acc.store(part + (size_t)s * EW);
+}
+// one lane per output that owns segments: t_j += sum_M eta_M (sum of the segments of M); the segments of a row are listed by matrix
+__global__ void __launch_bounds__(64) marlin_t_combine_kernel(const MarlinMatsDev mm, const MarlinEta eta, const uint32_t* __restrict__ part,
+                                                              uint32_t* __restrict__ t_out) {
+  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= mm.n_long_out) return;
+  uint32_t* dst = t_out + (size_t)mm.long_out[u] * FT::ABI_WORDS;
+  FT acc = FT::unpack32(dst), sum = FT::zero();
+  uint32_t cur = 3;
+  for (uint32_t s = mm.long_seg_lo[u]; s < mm.long_seg_lo[u + 1]; s++) {
+    const uint32_t mat = mm.segs[s].mat;
+    if (mat != cur) {
+      if (cur < 3) acc = acc + marlin_eta_of(eta, cur) * sum;
+      sum = FT::zero();
+      cur = mat;
+    }
+    sum = sum + FT::load(part + (size_t)s * EW);
+  }
+  if (cur < 3) acc = acc + marlin_eta_of(eta, cur) * sum;
+  acc.canonical().pack32(dst);
+}
+hipError_t marlin_t_evals_run(hipStream_t st, const MarlinMatsDev& mats, const uint32_t* eta_abi, const uint32_t* r, uint32_t* part,
+                              uint32_t* t_out, int* launches) {
+  if (launches) *launches = 0;
+  if (mats.rows == 0) return hipSuccess;
+  MarlinEta eta;
+  for (int k = 0; k < 3; k++) eta.e[k] = FT::from_abi(eta_abi + (size_t)k * FT::ABI_WORDS);
+  hipLaunchKernelGGL(marlin_t_short_kernel, dim3((mats.rows + 255) / 256), dim3(256), 0, st, mats, eta, r, t_out);
+  if (mats.n_segs) {
+    hipLaunchKernelGGL(marlin_t_seg_kernel, dim3(mats.n_segs), dim3(64), 0, st, mats, r, part);
+    hipLaunchKernelGGL(marlin_t_combine_kernel, dim3((mats.n_long_out + 63) / 64), dim3(64), 0, st, mats, eta, part, t_out);
+  }
+  if (launches) *launches = mats.n_segs ? 3 : 1;
+  return hipGetLastError();
+}
+
 }  // namespace
 
-#define PCD_CAT_(a, b) a##b
-#define PCD_CAT(a, b) PCD_CAT_(a, b)
 const FieldEntry* PCD_CAT(pcd_field_entry_, PCD_FIELD_IDX)() {
   static const FieldEntry e = {EW, FT::ABI_WORDS, FT::Params::TWO_ADICITY, make_tables, run, convert, spmv, small_abi, mul_sub_divz,
                                mixed_make_tables, mixed_run, mixed_mul_sub_divz, scale_canon, SETUP_CONSTS, setup_scalars, run_batched_entry, spmv3,
                                poly_scratch_words, poly_eval, poly_lincomb_run, vec_mul_run, vec_batch_inverse_run,
-                               poly_div_vanishing_run, poly_commit_scalars_run};
+                               poly_div_vanishing_run, poly_commit_scalars_run, marlin_lagrange_run, marlin_t_evals_run,
+                               PCD_CAT(pcd_marlin_sumcheck_ab_, PCD_FIELD_IDX)};
   return &e;
 }
 

@@ -1,0 +1,53 @@
+// One object per scalar field (compile with -DPCD_FIELD_IDX=0..3): the K9 kernels whose products are inlined (marlin.hip.h) -- the
+// differences behind r(alpha, .) on H and the rational sumcheck.  A unit of its own so that their 753-bit bodies compile beside the
+// field objects; inst_field.hip puts the two entries into its FieldEntry.
+#include "common.h"
+#include <string.h>
+
+#include "marlin.hip.h"
+
+namespace pcd {
+
+#if PCD_FIELD_IDX == 0
+typedef Fp<F298A, true> FTP;
+#elif PCD_FIELD_IDX == 1
+typedef Fp<F298B, true> FTP;
+#elif PCD_FIELD_IDX == 2
+typedef Fp<F753A, true> FTP;
+#elif PCD_FIELD_IDX == 3
+typedef Fp<F753B, true> FTP;
+#else
+#error "PCD_FIELD_IDX must be 0..3"
+#endif
+
+#define PCD_CAT_(a, b) a##b
+#define PCD_CAT(a, b) PCD_CAT_(a, b)
+
+// out_i = x - w^i for i < n (ABI words) and vh_abi = x^n - 1, formed on the host.  domain_consts = FftTables::consts of the domain
+// (DomainConsts and MixedConsts both start with its generator), tw = its tw_len resident powers; both null for n == 1
+hipError_t PCD_CAT(pcd_marlin_diffs_, PCD_FIELD_IDX)(hipStream_t st, const void* domain_consts, const uint32_t* tw, uint32_t tw_len,
+                                                     const uint32_t* x_abi, uint64_t n, uint32_t* out, uint32_t* vh_abi) {
+  FTP w = FTP::one();
+  if (domain_consts) memcpy(&w, domain_consts, sizeof w);
+  PolyAbiElt<FTP> x;
+  memcpy(x.w, x_abi, sizeof x.w);
+  (FTP::from_abi(x_abi).pow_u64(n) - FTP::one()).to_abi(vh_abi);
+  const uint64_t lanes = (n + MARLIN_LAG_E - 1) / MARLIN_LAG_E;
+  hipLaunchKernelGGL(marlin_lagrange_diffs<FTP>, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, st, tw, tw_len, w,
+                     tw ? w.pow_u64(tw_len) : FTP::one(), x, n, out);
+  return hipGetLastError();
+}
+
+hipError_t PCD_CAT(pcd_marlin_sumcheck_ab_, PCD_FIELD_IDX)(hipStream_t st, const uint32_t* alpha_abi, const uint32_t* beta_abi,
+                                                           const uint32_t* coeff_abi, const uint32_t* const row[3], const uint32_t* const col[3],
+                                                           const uint32_t* const rc[3], const uint32_t* const val[3], uint64_t n,
+                                                           uint32_t* a_out, uint32_t* b_out) {
+  if (n == 0) return hipSuccess;
+  const MarlinSumcheckConsts<FTP> k = marlin_sumcheck_consts<FTP>(alpha_abi, beta_abi, coeff_abi);
+  MarlinSumcheckIn in;
+  for (int m = 0; m < 3; m++) { in.row[m] = row[m]; in.col[m] = col[m]; in.rc[m] = rc[0] ? rc[m] : nullptr; in.val[m] = val[m]; }
+  hipLaunchKernelGGL(marlin_sumcheck_ab<FTP>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, k, in, n, a_out, b_out);
+  return hipGetLastError();
+}
+
+}  // namespace pcd
