@@ -190,7 +190,9 @@ int pcdhip_msm_config(pcdhip_ctx* ctx, int window_bits, int chunk);
 /* Sorting strategy of the (bucket, base) entries: 0 (default) MSD partition through LDS (per-workgroup bin
  * histograms, one global atomic per workgroup and bin, per-bin LDS counting sort); 1 single-pass binning into
  * per-bucket slots with an on-device fallback when a bucket overflows; 2 two-pass counting sort with one global
- * atomic per entry (also what small inputs use). */
+ * atomic per entry (also what small inputs use); 3 the partition of mode 0 with its direct write pass (entries stored
+ * one by one into their bins) where mode 0 stages a tile's entries in LDS and writes whole bin runs: the A/B partner of
+ * mode 0 and what it uses itself when no tile fits the LDS. */
 int pcdhip_msm_set_sort(pcdhip_ctx* ctx, int mode);
 /* Form of the bucket accumulation.  mode 0 (default) and 1: running sums (Jacobian / XYZZ mixed additions); 2: for the 753-bit G1
  * groups a PAIR TREE of affine additions whose inversions are shared (5M + 1S per addition instead of 7M + 4S, one divstep inversion per

@@ -305,7 +305,8 @@ class Context:
         return v.value
 
     def msm_set_sort(self, mode):
-        """0: LDS partition sort (default); 1: single-pass binning with on-device fallback; 2: two-pass counting sort."""
+        """0: LDS partition sort (default); 1: single-pass binning with on-device fallback; 2: two-pass counting sort;
+        3: the partition sort with its direct (unstaged) write pass."""
         self._check(lib().pcdhip_msm_set_sort(self._ctx, int(mode)))
 
     def msm_set_accumulate(self, mode, chunk=0, min_pairs=0):

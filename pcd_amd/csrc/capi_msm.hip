@@ -81,6 +81,18 @@ int make_side_streams(pcdhip_ctx* ctx) {
 }  // namespace
 
 namespace pcd {
+// developer knob (A/B of the partition sort's write pass, msm.hip.h): PCDHIP_COARSE_TILE = 0 selects the direct write pass, 256 .. 2048
+// bounds the staged pass's tile from above; anything else, or unset, leaves the choice to msm_stage_tile
+int msm_coarse_tile_knob() {
+  static const int knob = [] {
+    const char* e = getenv("PCDHIP_COARSE_TILE");
+    if (!e || *e < '0' || *e > '9') return -1;
+    const int v = atoi(e);
+    return v == 0 || (v >= (int)MSM_STAGE_TILE_MIN && v <= (int)MSM_STAGE_TILE_MAX) ? v : -1;
+  }();
+  return knob;
+}
+
 hipError_t zero_flagged(hipStream_t st, uint32_t* pts_dev, uint8_t* flags_dev, const uint8_t* flags_host, size_t n, size_t point_bytes) {
   if (!flags_host || !n) return hipSuccess;
   hipError_t e = hipMemcpyAsync(flags_dev, flags_host, n, hipMemcpyHostToDevice, st);
@@ -422,7 +434,7 @@ int pcdhip_msm_config(pcdhip_ctx* ctx, int window_bits, int chunk) {
   return PCDHIP_OK;
 }
 int pcdhip_msm_set_sort(pcdhip_ctx* ctx, int mode) {
-  if (!ctx || mode < 0 || mode > 2) return PCDHIP_E_ARG;
+  if (!ctx || mode < 0 || mode > 3) return PCDHIP_E_ARG;  // (3: the partition sort of mode 0 with the direct write pass)
   ctx->msm_sort = (ctx->msm_sort & ~15) | mode;  // (the higher bits carry pcdhip_msm_set_accumulate's choice: msm.hip.h msm_run)
   return PCDHIP_OK;
 }

@@ -7,7 +7,7 @@
 // bucket method differently from upstream (which parallelises over windows only):
 //
 //   1. sort          signed digits of every scalar -> (bucket, base index) entries sorted by bucket: an MSD partition through LDS
-//                    (msm_coarse_kernel x2, msm_bin_scan_kernel, msm_bin_sort_kernel); counting-sort and single-pass binning
+//                    (msm_coarse_kernel, msm_coarse_staged_kernel, msm_bin_scan_kernel, msm_bin_sort_kernel); counting-sort and single-pass binning
 //                    variants stay selectable (msm_digits_kernel, scan_*)
 //   2. msm_accumulate fixed-size chunks of the sorted list, one lane (or 2 / 3 lanes: lane-split extension fields) per chunk:
 //                    every lane does the same number of mixed additions whatever the scalar distribution; runs that cross
@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 #include <vector>
 
@@ -189,8 +190,9 @@ __global__ void __launch_bounds__(256) msm_digits_kernel(const uint32_t* __restr
 //   pass 0  msm_coarse_kernel<false>: per-workgroup LDS histogram over the bins of a tile of scalars, one global atomic
 //           per (workgroup, non-empty bin);  scalars equal to one go, wave-aggregated, to the pseudo bucket's list
 //   scan    bin bases
-//   pass 1  msm_coarse_kernel<true>: the same LDS histogram, one global atomic per (workgroup, bin) to reserve a run in
-//           the bin, then the entries (key, base index) are written into that run through LDS cursors
+//   pass 1  msm_coarse_staged_kernel: the tile read once; the same LDS histogram, one global atomic per (workgroup, bin) to reserve a
+//           run in the bin; the tile's entries ordered by bin in LDS and written as whole runs.  msm_coarse_kernel<true> (entries
+//           written one by one through LDS cursors) where no tile fits the LDS, and as the A/B partner
 //   pass 2  msm_bin_sort_kernel: one workgroup per bin: LDS counting sort of its entries by the low key bits; writes
 //           the final base-index list and the per-key offsets (bins are in key order, so no global scan is needed)
 // Global atomics drop from n W to ~2 n W / TILE_ENTRIES_PER_BIN; everything else is LDS atomics and streaming.
@@ -290,6 +292,155 @@ __global__ void __launch_bounds__(256) msm_coarse_kernel(const uint32_t* __restr
       if (++j == Wg) { j = 0; g++; }
     }
   }
+}
+
+// ---- staged write pass (pass 1 of the partition sort; msm_coarse_kernel<NS, true> stays as the fallback and the A/B partner)
+// The direct write pass sends the 15 digits of a lane's scalar to 15 unrelated bins: every wave-level store is 64 separate 8-byte
+// requests to 64 lines, and the scalars are read and recoded three times (pass 0 included).  Here a workgroup reads its tile ONCE
+// into registers, counts, reserves its runs exactly as before (one global atomic per non-empty bin), orders the tile's entries by bin
+// in LDS as 4-byte words, and then walks that buffer linearly: consecutive lanes store consecutive entries of a bin's run, so a
+// wave's store covers a handful of contiguous runs.  The order of the entries inside a bin changes (it depends on atomics in both
+// forms); the 8-byte entry format and everything behind this pass do not.
+// Staged word: low key bits | sign | group g (the window is g Wg + j, and j is the bin's top bits) | scalar index inside the tile.
+constexpr int MSM_STAGE_G_BITS = 6, MSM_STAGE_IDX_BITS = 11;
+constexpr uint32_t MSM_STAGE_TILE_MAX = 1u << MSM_STAGE_IDX_BITS, MSM_STAGE_TILE_MIN = 256;  // scalars per workgroup
+constexpr int MSM_STAGE_W_MAX = 1 << MSM_STAGE_G_BITS;                                        // windows (g < W)
+constexpr int MSM_STAGE_SIGN_AT = MSM_BIN_SHIFT, MSM_STAGE_G_AT = MSM_BIN_SHIFT + 1, MSM_STAGE_IDX_AT = MSM_STAGE_G_AT + MSM_STAGE_G_BITS;
+static_assert(MSM_STAGE_IDX_AT + MSM_STAGE_IDX_BITS <= 32, "staged word: low key bits, sign, group and tile index in 32 bits");
+// LDS of a workgroup: the word buffer (tile x W) and three arrays over the bins (cursors, local offsets + total, run bases).
+// The budget is the CU's 160 KiB less 8 KiB for the kernel's static arrays and the allocation granule (the headline -- 2 048 x 15 words and
+// 2 048 bins, the upper half of them empty under signed digits -- takes 144 KiB and 16 bytes).
+constexpr size_t MSM_STAGE_LDS_BUDGET = 152u * 1024u;
+constexpr uint32_t MSM_STAGE_MIN_RUN = 8;  // entries a (tile, bin) run must hold on average: 64 bytes, or the stores are no better than the direct ones
+PCD_HD constexpr size_t msm_stage_lds_bytes(uint32_t tile, int W, uint32_t nbins) { return 4 * ((size_t)tile * (size_t)W + 3 * (size_t)nbins + 4); }
+// scalars per workgroup of the staged pass: the largest power of two in [MSM_STAGE_TILE_MIN, MSM_STAGE_TILE_MAX] whose footprint fits the
+// budget; 0 = none does, or the runs it would write are too short to be worth staging (msm_run then launches the direct pass)
+PCD_HD constexpr uint32_t msm_stage_tile(int W, uint32_t nbins) {
+  if (W < 1 || W > MSM_STAGE_W_MAX || nbins < 1) return 0;
+  for (uint32_t t = MSM_STAGE_TILE_MAX; t >= MSM_STAGE_TILE_MIN; t >>= 1)
+    if (msm_stage_lds_bytes(t, W, nbins) <= MSM_STAGE_LDS_BUDGET) return (uint64_t)t * (uint32_t)W >= (uint64_t)MSM_STAGE_MIN_RUN * nbins ? t : 0;
+  return 0;
+}
+// PCDHIP_COARSE_TILE (capi_msm.hip, read once; developer knob for the A/B): 0 = the direct write pass, 256 .. 2048 = an upper bound of the
+// staged tile, unset (-1) = msm_stage_tile's choice
+int msm_coarse_tile_knob();
+
+constexpr int msm_stage_block(int TILE) { return TILE < 1024 ? TILE : 1024; }
+template <int NS, int TILE>
+__global__ void __launch_bounds__(msm_stage_block(TILE)) msm_coarse_staged_kernel(const uint32_t* __restrict__ scalars, uint32_t n, int c, int W, int Wg,
+                                                                                  uint32_t n_total, uint32_t base_offset, uint32_t nbins,
+                                                                                  uint32_t* __restrict__ gbin /* cursors (start at the bin bases) */,
+                                                                                  uint64_t* __restrict__ entries, const uint32_t* __restrict__ inf_bits) {
+  constexpr int BLOCK = msm_stage_block(TILE), K = TILE / BLOCK, NW = BLOCK / 64;
+  static_assert(TILE >= (int)MSM_STAGE_TILE_MIN && TILE <= (int)MSM_STAGE_TILE_MAX && TILE % BLOCK == 0, "tile");
+  extern __shared__ uint32_t lds[];
+  uint32_t* cur = lds;                  // nbins: counts, then local cursors
+  uint32_t* loff = cur + nbins;         // nbins + 1: start of every bin's run inside the tile's buffer; [nbins] = entries of the tile
+  uint32_t* rdelta = loff + nbins + 1;  // nbins: (reserved run base in `entries`) - loff
+  uint32_t* buf = rdelta + nbins;       // TILE x W staged words, ordered by bin
+  __shared__ uint32_t s_wsum[NW];
+  const uint32_t t = threadIdx.x, tile0 = blockIdx.x * TILE;
+  for (uint32_t b = t; b < nbins; b += BLOCK) cur[b] = 0;
+  // 1. read once: K scalars per lane stay in registers (same liveness rule as the direct pass: bases at infinity, zero and one skipped)
+  uint32_t s[K][NS];
+  bool live[K];
+#pragma unroll
+  for (int kk = 0; kk < K; kk++) {
+    const uint32_t i = tile0 + t + kk * BLOCK;
+    live[kk] = i < n && !msm_base_is_inf(inf_bits, base_offset + i);
+    uint32_t hi = 0;
+#pragma unroll
+    for (int q = 0; q < NS; q++) { s[kk][q] = live[kk] ? scalars[(size_t)i * NS + q] : 0u; if (q) hi |= s[kk][q]; }
+    if (hi == 0 && s[kk][0] <= 1) live[kk] = false;
+  }
+  __syncthreads();
+  // 2. count
+#pragma unroll
+  for (int kk = 0; kk < K; kk++) {
+    if (!live[kk]) continue;
+    int j = 0;
+    uint32_t carry = 0, neg;
+    for (int w = 0; w < W; w++) {
+      uint32_t d = msm_signed(msm_digit<NS>(s[kk], w, c), c, carry, neg);
+      if (d != 0) atomicAdd(&cur[((((uint32_t)j << c) | d)) >> MSM_BIN_SHIFT], 1u);
+      if (++j == Wg) j = 0;
+    }
+  }
+  __syncthreads();
+  // 3. exclusive scan of the tile's histogram (consecutive bins per lane, wave scan, wave totals) and one global atomic per non-empty bin
+  const uint32_t per = (nbins + BLOCK - 1) / BLOCK;
+  const uint32_t blo = min(nbins, t * per), bhi = min(nbins, blo + per);
+  uint32_t acc = 0;
+  for (uint32_t b = blo; b < bhi; b++) acc += cur[b];
+  const uint32_t lane = t & 63, wv = t >> 6;
+  uint32_t incl = acc;
+  for (int d = 1; d < 64; d <<= 1) { uint32_t o = __shfl_up(incl, d, 64); if ((int)lane >= d) incl += o; }
+  if (lane == 63) s_wsum[wv] = incl;
+  __syncthreads();
+  uint32_t run = incl - acc;
+  for (uint32_t q = 0; q < wv; q++) run += s_wsum[q];
+  for (uint32_t b = blo; b < bhi; b++) {
+    const uint32_t cnt = cur[b];
+    loff[b] = run;
+    cur[b] = run;
+    if (cnt) rdelta[b] = atomicAdd(&gbin[b], cnt) - run;
+    run += cnt;
+  }
+  if (t == BLOCK - 1) loff[nbins] = run;  // (the last lane's range ends at nbins or is empty: its running sum is the tile's total)
+  __syncthreads();
+  // 4. place: the digits again, from the registers; the entry's slot comes from the local cursor of its bin
+#pragma unroll
+  for (int kk = 0; kk < K; kk++) {
+    if (!live[kk]) continue;
+    int g = 0, j = 0;
+    uint32_t carry = 0, neg;
+    for (int w = 0; w < W; w++) {
+      uint32_t d = msm_signed(msm_digit<NS>(s[kk], w, c), c, carry, neg);
+      if (d != 0) {
+        const uint32_t key = ((uint32_t)j << c) | d;
+        const uint32_t q = atomicAdd(&cur[key >> MSM_BIN_SHIFT], 1u);
+        buf[q] = (key & ((1u << MSM_BIN_SHIFT) - 1u)) | (neg ? 1u << MSM_STAGE_SIGN_AT : 0u) | ((uint32_t)g << MSM_STAGE_G_AT) |
+                 ((t + kk * BLOCK) << MSM_STAGE_IDX_AT);
+      }
+      if (++j == Wg) { j = 0; g++; }
+    }
+  }
+  __syncthreads();
+  // 5. write out: slot q belongs to the last bin whose run starts at or before q (empty bins share their successor's start)
+  const uint32_t total = loff[nbins];
+  for (uint32_t q = t; q < total; q += BLOCK) {
+    const uint32_t word = buf[q];
+    uint32_t lo = 0, hi = nbins;
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (loff[mid] <= q) lo = mid; else hi = mid;
+    }
+    const uint32_t key = (lo << MSM_BIN_SHIFT) | (word & ((1u << MSM_BIN_SHIFT) - 1u));
+    const uint32_t g = (word >> MSM_STAGE_G_AT) & ((1u << MSM_STAGE_G_BITS) - 1u);
+    const uint32_t neg = (word >> MSM_STAGE_SIGN_AT) & 1u ? MSM_NEG : 0u;
+    const uint32_t idx = (g * n_total + base_offset + tile0 + (word >> MSM_STAGE_IDX_AT)) | neg;
+    entries[rdelta[lo] + q] = ((uint64_t)key << 32) | (uint64_t)idx;
+  }
+}
+// dynamic LDS above 64 KiB has to be allowed once per function and device
+template <int NS, int TILE>
+hipError_t msm_coarse_staged_launch(hipStream_t st, uint32_t tiles, size_t lds, const uint32_t* scalars, uint32_t n, int c, int W, int Wg,
+                                    uint32_t n_total, uint32_t base_offset, uint32_t nbins, uint32_t* gbin, uint64_t* entries,
+                                    const uint32_t* inf_bits) {
+  static std::atomic<uint64_t> allowed{0};  // bit d: done on device d
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  const uint64_t bit = 1ull << (dev & 63);
+  if (!(allowed.load(std::memory_order_relaxed) & bit)) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_coarse_staged_kernel<NS, TILE>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)MSM_STAGE_LDS_BUDGET);
+    if (e != hipSuccess) return e;
+    allowed.fetch_or(bit, std::memory_order_relaxed);
+  }
+  hipLaunchKernelGGL((msm_coarse_staged_kernel<NS, TILE>), dim3(tiles), dim3(msm_stage_block(TILE)), lds, st, scalars, n, c, W, Wg, n_total,
+                     base_offset, nbins, gbin, entries, inf_bits);
+  return hipSuccess;
 }
 
 // bin_base: exclusive scan of the bin counts (nbins + 1 values) + the list offsets of the pseudo bucket
@@ -1710,7 +1861,14 @@ hipError_t msm_run(MsmWorkspace& ws, hipStream_t st, const MsmBasesView& bv, con
   const bool use_slots = single_pass && (double)pl.nkeys * cap * 4.0 <= 1.5e9;
   // default: MSD partition through LDS (needs whole bins of 2^MSM_BIN_SHIFT keys and an LDS histogram per workgroup)
   const uint32_t nbins = pl.nkeys >> MSM_BIN_SHIFT;
-  const bool use_partition = sort_mode == 0 && pl.c >= MSM_BIN_SHIFT && nbins >= 1 && nbins <= MSM_MAX_BINS && n >= 4096;
+  const bool use_partition = (sort_mode == 0 || sort_mode == 3) && pl.c >= MSM_BIN_SHIFT && nbins >= 1 && nbins <= MSM_MAX_BINS && n >= 4096;
+  // its write pass: staged through LDS in tiles of stage_tile scalars, or (0: pcdhip_msm_set_sort 3, the knob, or no tile fits) direct
+  uint32_t stage_tile = 0;
+  if (use_partition && sort_mode == 0) {
+    const int knob = msm_coarse_tile_knob();
+    stage_tile = knob == 0 ? 0u : msm_stage_tile(pl.W, nbins);
+    while (knob > 0 && stage_tile > (uint32_t)knob) stage_tile >>= 1;
+  }
   uint32_t* slots = nullptr;
   if (use_slots) { PCD_HIP_TRY(ws.ensure(WS_SLOTS, (size_t)pl.nkeys * cap * 4)); slots = (uint32_t*)ws.buf[WS_SLOTS]; }
 
@@ -1757,8 +1915,16 @@ hipError_t msm_run(MsmWorkspace& ws, hipStream_t st, const MsmBasesView& bv, con
     PCD_HIP_TRY(mark(1));
     hipLaunchKernelGGL(msm_bin_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, nbins, bin_base, cursor, ones_count, off, pl.nkeys);
     PCD_HIP_TRY(mark(2));
-    hipLaunchKernelGGL((msm_coarse_kernel<NS, true>), dim3(tiles), dim3(256), (size_t)nbins * 4, st, scalars_dev, n, pl.c, pl.W, Wg, bv.n_total,
-                       bv.offset, nbins, cursor, entries, ones_count, ones_idx, SBITS, err, bv.inf_bits);
+    if (stage_tile) {
+      const uint32_t stiles = (n + stage_tile - 1) / stage_tile;
+      const size_t lds = msm_stage_lds_bytes(stage_tile, pl.W, nbins);
+#define PCD_STAGED(T) msm_coarse_staged_launch<NS, T>(st, stiles, lds, scalars_dev, n, pl.c, pl.W, Wg, bv.n_total, bv.offset, nbins, cursor, entries, bv.inf_bits)
+      PCD_HIP_TRY(stage_tile == 2048 ? PCD_STAGED(2048) : stage_tile == 1024 ? PCD_STAGED(1024) : stage_tile == 512 ? PCD_STAGED(512) : PCD_STAGED(256));
+#undef PCD_STAGED
+    } else {
+      hipLaunchKernelGGL((msm_coarse_kernel<NS, true>), dim3(tiles), dim3(256), (size_t)nbins * 4, st, scalars_dev, n, pl.c, pl.W, Wg, bv.n_total,
+                         bv.offset, nbins, cursor, entries, ones_count, ones_idx, SBITS, err, bv.inf_bits);
+    }
     hipLaunchKernelGGL(msm_bin_sort_kernel, dim3(nbins), dim3(256), 0, st, entries, bin_base, sorted, off);
     PCD_HIP_TRY(mark(3));
     src = {sorted, nullptr, ones_idx, nullptr, 0u, ones_key};
