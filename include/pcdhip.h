@@ -192,8 +192,14 @@ int pcdhip_msm_config(pcdhip_ctx* ctx, int window_bits, int chunk);
  * per-bucket slots with an on-device fallback when a bucket overflows; 2 two-pass counting sort with one global
  * atomic per entry (also what small inputs use); 3 the partition of mode 0 with its direct write pass (entries stored
  * one by one into their bins) where mode 0 stages a tile's entries in LDS and writes whole bin runs: the A/B partner of
- * mode 0 and what it uses itself when no tile fits the LDS. */
+ * mode 0 and what it uses itself when no tile fits the LDS; 4 mode 0 with the two-read per-bin sort (every entry of a bin read twice,
+ * every sorted index stored on its own) where modes 0 and 3 order a bin that fits the LDS there from one read and write it out in whole
+ * lines: the A/B partner of mode 0 for that kernel (PCDHIP_BIN_STAGE=0 in the environment selects it for a whole process). */
 int pcdhip_msm_set_sort(pcdhip_ctx* ctx, int mode);
+/* Developer and test knob of the per-bin sort of modes 0 and 3: a bin of at most `cap` entries is ordered in LDS from one read, a larger
+ * one takes the two-read form inside the same launch.  -1 (default): 18 432, what the LDS holds; 0: the two-read kernel of mode 4;
+ * 1 .. 18 432: that threshold.  Results are identical for every value. */
+int pcdhip_msm_set_bin_stage(pcdhip_ctx* ctx, int cap);
 /* Form of the bucket accumulation.  mode 0 (default) and 1: running sums (Jacobian / XYZZ mixed additions); 2: for the 753-bit G1
  * groups a PAIR TREE of affine additions whose inversions are shared (5M + 1S per addition instead of 7M + 4S, one divstep inversion per
  * lane and level; msm.hip.h msm_pair_tree_kernel) -- measured -9 % on the accumulation and -5 % on an MSM of 2^20 uniform scalars,

@@ -93,6 +93,15 @@ int msm_coarse_tile_knob() {
   return knob;
 }
 
+// developer knob (A/B of the partition sort's per-bin sort, msm.hip.h): PCDHIP_BIN_STAGE = 0 selects msm_bin_sort_kernel for the whole process
+int msm_bin_stage_knob() {
+  static const int knob = [] {
+    const char* e = getenv("PCDHIP_BIN_STAGE");
+    return e && e[0] == '0' && e[1] == 0 ? 0 : -1;
+  }();
+  return knob;
+}
+
 hipError_t zero_flagged(hipStream_t st, uint32_t* pts_dev, uint8_t* flags_dev, const uint8_t* flags_host, size_t n, size_t point_bytes) {
   if (!flags_host || !n) return hipSuccess;
   hipError_t e = hipMemcpyAsync(flags_dev, flags_host, n, hipMemcpyHostToDevice, st);
@@ -434,8 +443,18 @@ int pcdhip_msm_config(pcdhip_ctx* ctx, int window_bits, int chunk) {
   return PCDHIP_OK;
 }
 int pcdhip_msm_set_sort(pcdhip_ctx* ctx, int mode) {
-  if (!ctx || mode < 0 || mode > 3) return PCDHIP_E_ARG;  // (3: the partition sort of mode 0 with the direct write pass)
+  if (!ctx || mode < 0 || mode > 4) return PCDHIP_E_ARG;  // (3 / 4: the partition sort of mode 0 with the direct write pass / the two-read bin sort)
   ctx->msm_sort = (ctx->msm_sort & ~15) | mode;  // (the higher bits carry pcdhip_msm_set_accumulate's choice: msm.hip.h msm_run)
+  return PCDHIP_OK;
+}
+int pcdhip_msm_set_bin_stage(pcdhip_ctx* ctx, int cap) {
+  if (!ctx || cap < -1 || cap > (int)MSM_BIN_STAGE_CAP) return PCDHIP_E_ARG;
+  // (every workspace an msm_run of this context may be given: its own, the proof's and the pipeline's, on every device)
+  const std::vector<pcdhip_ctx*> one{ctx};
+  for (pcdhip_ctx* c : ctx->peers.empty() ? one : ctx->peers) {
+    c->msm_ws.bin_stage = cap;
+    for (pcd::MsmWorkspace& w : c->g16_ws) w.bin_stage = cap;
+  }
   return PCDHIP_OK;
 }
 int pcdhip_msm_set_accumulate(pcdhip_ctx* ctx, int mode, int chunk, int min_pairs) {

@@ -7,7 +7,7 @@
 // bucket method differently from upstream (which parallelises over windows only):
 //
 //   1. sort          signed digits of every scalar -> (bucket, base index) entries sorted by bucket: an MSD partition through LDS
-//                    (msm_coarse_kernel, msm_coarse_staged_kernel, msm_bin_scan_kernel, msm_bin_sort_kernel); counting-sort and single-pass binning
+//                    (msm_coarse_kernel, msm_coarse_staged_kernel, msm_bin_scan_kernel, msm_bin_sort_staged_kernel); counting-sort and single-pass binning
 //                    variants stay selectable (msm_digits_kernel, scan_*)
 //   2. msm_accumulate fixed-size chunks of the sorted list, one lane (or 2 / 3 lanes: lane-split extension fields) per chunk:
 //                    every lane does the same number of mixed additions whatever the scalar distribution; runs that cross
@@ -193,8 +193,10 @@ __global__ void __launch_bounds__(256) msm_digits_kernel(const uint32_t* __restr
 //   pass 1  msm_coarse_staged_kernel: the tile read once; the same LDS histogram, one global atomic per (workgroup, bin) to reserve a
 //           run in the bin; the tile's entries ordered by bin in LDS and written as whole runs.  msm_coarse_kernel<true> (entries
 //           written one by one through LDS cursors) where no tile fits the LDS, and as the A/B partner
-//   pass 2  msm_bin_sort_kernel: one workgroup per bin: LDS counting sort of its entries by the low key bits; writes
-//           the final base-index list and the per-key offsets (bins are in key order, so no global scan is needed)
+//   pass 2  msm_bin_sort_staged_kernel: one workgroup per bin: LDS counting sort of its entries by the low key bits; writes
+//           the final base-index list and the per-key offsets (bins are in key order, so no global scan is needed).  A bin that
+//           fits the LDS is read once, ordered there and written out as whole lines; a larger one is read twice and its indices
+//           stored one by one, which is all msm_bin_sort_kernel (the A/B partner) does
 // Global atomics drop from n W to ~2 n W / TILE_ENTRIES_PER_BIN; everything else is LDS atomics and streaming.
 #ifndef PCD_SORT_UNROLL
 #define PCD_SORT_UNROLL 4
@@ -471,49 +473,155 @@ static __global__ void __launch_bounds__(1024) msm_bin_scan_kernel(const uint32_
   }
 }
 
-// one workgroup per bin: counting sort of its entries by the low MSM_BIN_SHIFT key bits
-static __global__ void __launch_bounds__(256) msm_bin_sort_kernel(const uint64_t* __restrict__ entries, const uint32_t* __restrict__ bin_base,
-                                                                  uint32_t* __restrict__ sorted_idx, uint32_t* __restrict__ off) {
+// ---- per-bin counting sort (pass 2 of the partition sort): one workgroup per bin, by the low MSM_BIN_SHIFT key bits
+// exclusive scan of a bin's 512 counters by BLOCK lanes (consecutive counters per lane, wave scan, then the wave totals): writes the
+// bin's `off` values (lo + start of the key inside the bin) and leaves hbase + that start in the counter
+template <int BLOCK>
+__device__ __forceinline__ void msm_bin_scan_counters(uint32_t* hist, uint32_t* wsum, uint32_t lo, uint32_t hbase, uint32_t* __restrict__ off_b) {
+  constexpr int KB = 1 << MSM_BIN_SHIFT, PER = KB / BLOCK;
+  static_assert(PER >= 1 && PER * BLOCK == KB && BLOCK % 64 == 0, "counters per lane");
+  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  uint32_t c[PER], sum = 0;
+#pragma unroll
+  for (int k = 0; k < PER; k++) { c[k] = hist[PER * t + k]; sum += c[k]; }
+  uint32_t incl = sum;
+  for (int d = 1; d < 64; d <<= 1) { uint32_t o = __shfl_up(incl, d, 64); if ((int)lane >= d) incl += o; }
+  if (lane == 63) wsum[wv] = incl;
+  __syncthreads();
+  uint32_t ex = incl - sum;
+  for (uint32_t q = 0; q < wv; q++) ex += wsum[q];
+#pragma unroll
+  for (int k = 0; k < PER; k++) {
+    hist[PER * t + k] = hbase + ex;
+    off_b[PER * t + k] = lo + ex;
+    ex += c[k];
+  }
+  __syncthreads();
+}
+// the two-read form: the bin's entries read once to count and once more to scatter, every sorted index stored on its own
+template <int BLOCK>
+__device__ __forceinline__ void msm_bin_sort_two_read(const uint64_t* __restrict__ entries, uint32_t lo, uint32_t hi, uint32_t* __restrict__ sorted_idx,
+                                                      uint32_t* __restrict__ off_b, uint32_t* hist, uint32_t* wsum) {
   constexpr uint32_t KB = 1u << MSM_BIN_SHIFT;
-  __shared__ uint32_t hist[KB];
-  __shared__ uint32_t wsum[4];
-  const uint32_t b = blockIdx.x, lo = bin_base[b], hi = bin_base[b + 1];
-  for (uint32_t k = threadIdx.x; k < KB; k += blockDim.x) hist[k] = 0;
+  for (uint32_t k = threadIdx.x; k < KB; k += BLOCK) hist[k] = 0;
   __syncthreads();
   // (four entries per lane in flight: the loop is a chain of global load -> LDS atomic -> scattered store latencies)
-  for (uint32_t p0 = lo + threadIdx.x; p0 < hi; p0 += MSM_SORT_UNROLL * blockDim.x) {
+  for (uint32_t p0 = lo + threadIdx.x; p0 < hi; p0 += MSM_SORT_UNROLL * BLOCK) {
     uint32_t kk[MSM_SORT_UNROLL];
 #pragma unroll
-    for (int u = 0; u < MSM_SORT_UNROLL; u++) { uint32_t p = p0 + u * blockDim.x; kk[u] = p < hi ? (uint32_t)(entries[p] >> 32) & (KB - 1) : KB; }
+    for (int u = 0; u < MSM_SORT_UNROLL; u++) { uint32_t p = p0 + u * BLOCK; kk[u] = p < hi ? (uint32_t)(entries[p] >> 32) & (KB - 1) : KB; }
 #pragma unroll
     for (int u = 0; u < MSM_SORT_UNROLL; u++) if (kk[u] < KB) atomicAdd(&hist[kk[u]], 1u);
   }
   __syncthreads();
-  // exclusive scan of the 512 counters: two per lane, wave scan, then the four wave totals
-  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  uint32_t c0 = hist[2 * t], c1 = hist[2 * t + 1];
-  uint32_t incl = c0 + c1;
-  for (int d = 1; d < 64; d <<= 1) { uint32_t o = __shfl_up(incl, d, 64); if ((int)lane >= d) incl += o; }
-  if (lane == 63) wsum[wv] = incl;
-  __syncthreads();
-  uint32_t before = 0;
-  for (uint32_t q = 0; q < wv; q++) before += wsum[q];
-  uint32_t ex = lo + before + incl - (c0 + c1);
-  hist[2 * t] = ex;
-  hist[2 * t + 1] = ex + c0;
-  off[(size_t)b * KB + 2 * t] = ex;
-  off[(size_t)b * KB + 2 * t + 1] = ex + c0;
-  __syncthreads();
-  for (uint32_t p0 = lo + threadIdx.x; p0 < hi; p0 += MSM_SORT_UNROLL * blockDim.x) {
+  msm_bin_scan_counters<BLOCK>(hist, wsum, lo, lo, off_b);
+  for (uint32_t p0 = lo + threadIdx.x; p0 < hi; p0 += MSM_SORT_UNROLL * BLOCK) {
     uint64_t e[MSM_SORT_UNROLL];
     uint32_t pos[MSM_SORT_UNROLL];
 #pragma unroll
-    for (int u = 0; u < MSM_SORT_UNROLL; u++) { uint32_t p = p0 + u * blockDim.x; e[u] = p < hi ? entries[p] : ~0ull; }
+    for (int u = 0; u < MSM_SORT_UNROLL; u++) { uint32_t p = p0 + u * BLOCK; e[u] = p < hi ? entries[p] : ~0ull; }
 #pragma unroll
     for (int u = 0; u < MSM_SORT_UNROLL; u++) if (e[u] != ~0ull) pos[u] = atomicAdd(&hist[(uint32_t)(e[u] >> 32) & (KB - 1)], 1u);
 #pragma unroll
     for (int u = 0; u < MSM_SORT_UNROLL; u++) if (e[u] != ~0ull) sorted_idx[pos[u]] = (uint32_t)e[u];
   }
+}
+static __global__ void __launch_bounds__(256) msm_bin_sort_kernel(const uint64_t* __restrict__ entries, const uint32_t* __restrict__ bin_base,
+                                                                  uint32_t* __restrict__ sorted_idx, uint32_t* __restrict__ off) {
+  constexpr uint32_t KB = 1u << MSM_BIN_SHIFT;
+  __shared__ uint32_t hist[KB];
+  __shared__ uint32_t wsum[4];
+  const uint32_t b = blockIdx.x;
+  msm_bin_sort_two_read<256>(entries, bin_base[b], bin_base[b + 1], sorted_idx, off + (size_t)b * KB, hist, wsum);
+}
+
+// ---- staged form (the default; msm_bin_sort_kernel stays as the A/B partner: pcdhip_msm_set_sort 4, PCDHIP_BIN_STAGE=0)
+// The two-read form reads every 8-byte entry of its bin twice and stores every sorted index on its own: a wave's store is 64 four-byte
+// requests to 64 places.  Here a bin of at most `cap` entries is read ONCE, coalesced, into registers (index word + low key bits); the
+// counting atomic returns the entry's rank inside its key, so after the scan of the counters every index word goes to its final place in an
+// LDS buffer, and the buffer is written to sorted_idx linearly, 16 bytes per lane.  The buffer starts at the bin's offset inside its
+// 16-byte line of sorted_idx (lo & 3), so the LDS reads and the global stores are aligned together.  A larger bin -- every bin of a
+// list too long for LDS -- takes the two-read form inside the same launch; the choice is the workgroup's own, from bin_base.  The order of
+// the entries inside a key changes (it depends on atomics in both forms); nothing behind the sort depends on it.
+constexpr int MSM_BIN_STAGE_BLOCK = 512, MSM_BIN_STAGE_PER = 36;                       // lanes per workgroup, entries per lane
+constexpr uint32_t MSM_BIN_STAGE_CAP = MSM_BIN_STAGE_BLOCK * MSM_BIN_STAGE_PER;       // 18 432 entries: the headline's fullest bin holds 16 911
+// LDS of a workgroup, all of it dynamic: the word buffer (+ 4: the alignment shift), the 512 counters, the wave totals.  Two workgroups fit a CU.
+PCD_HD constexpr size_t msm_bin_stage_lds_bytes() { return 4 * ((size_t)MSM_BIN_STAGE_CAP + 4 + (1u << MSM_BIN_SHIFT) + MSM_BIN_STAGE_BLOCK / 64); }
+static_assert(2 * msm_bin_stage_lds_bytes() <= 160u * 1024u && msm_bin_stage_lds_bytes() <= 78u * 1024u, "two workgroups per CU");
+// PCDHIP_BIN_STAGE (capi_msm.hip, read once; developer knob for the A/B): 0 = msm_bin_sort_kernel, unset (-1) = the staged kernel
+int msm_bin_stage_knob();
+
+static __global__ void __launch_bounds__(MSM_BIN_STAGE_BLOCK, 4) msm_bin_sort_staged_kernel(const uint64_t* __restrict__ entries,
+                                                                                             const uint32_t* __restrict__ bin_base,
+                                                                                             uint32_t* __restrict__ sorted_idx /* 16-byte aligned */,
+                                                                                             uint32_t* __restrict__ off, uint32_t cap) {
+  constexpr uint32_t KB = 1u << MSM_BIN_SHIFT;
+  constexpr int BLOCK = MSM_BIN_STAGE_BLOCK, PER = MSM_BIN_STAGE_PER;
+  static_assert(MSM_BIN_STAGE_CAP % 4 == 0 && MSM_BIN_STAGE_CAP < (1u << (32 - MSM_BIN_SHIFT)), "16-byte lines; the rank beside the key");
+  extern __shared__ __attribute__((aligned(16))) uint32_t bin_lds[];
+  uint32_t* buf = bin_lds;                        // MSM_BIN_STAGE_CAP + 4 words: buf[sh + q] becomes sorted_idx[lo + q]
+  uint32_t* hist = buf + MSM_BIN_STAGE_CAP + 4;   // KB
+  uint32_t* wsum = hist + KB;                     // BLOCK / 64
+  const uint32_t b = blockIdx.x, t = threadIdx.x, lo = bin_base[b], hi = bin_base[b + 1], m = hi - lo;
+  uint32_t* off_b = off + (size_t)b * KB;
+  if (m > min(cap, MSM_BIN_STAGE_CAP)) { msm_bin_sort_two_read<BLOCK>(entries, lo, hi, sorted_idx, off_b, hist, wsum); return; }
+  for (uint32_t k = t; k < KB; k += BLOCK) hist[k] = 0;
+  __syncthreads();
+  // 1. read once and count: every load of the lane is issued before the first atomic waits for one; the atomic's return value is the
+  //    entry's rank inside its key
+  uint64_t e[PER];
+#pragma unroll
+  for (int u = 0; u < PER; u++) { const uint32_t p = lo + t + u * BLOCK; e[u] = p < hi ? entries[p] : 0ull; }
+  uint32_t idx[PER], kr[PER];  // index word; low key bits | rank << MSM_BIN_SHIFT (~0: no entry)
+#pragma unroll
+  for (int u = 0; u < PER; u++) {
+    const uint32_t k = (uint32_t)(e[u] >> 32) & (KB - 1);
+    idx[u] = (uint32_t)e[u];
+    kr[u] = ~0u;
+    if (lo + t + u * BLOCK < hi) kr[u] = k | (atomicAdd(&hist[k], 1u) << MSM_BIN_SHIFT);
+  }
+  __syncthreads();
+  // 2. scan; the counters become the start of every key inside the buffer
+  const uint32_t sh = lo & 3u;
+  msm_bin_scan_counters<BLOCK>(hist, wsum, lo, sh, off_b);
+  // 3. place
+#pragma unroll
+  for (int u = 0; u < PER; u++)
+    if (kr[u] != ~0u) buf[hist[kr[u] & (KB - 1)] + (kr[u] >> MSM_BIN_SHIFT)] = idx[u];
+  __syncthreads();
+  // 4. write out: four words per lane, whole 16-byte lines except at the bin's two ends
+  const uint32_t end = sh + m;
+  uint32_t* dst = sorted_idx + (lo - sh);
+  for (uint32_t q = 4 * t; q < end; q += 4 * BLOCK) {
+    if (q >= sh && q + 4 <= end) {
+      *reinterpret_cast<uint4*>(dst + q) = *reinterpret_cast<const uint4*>(buf + q);
+    } else {
+#pragma unroll
+      for (uint32_t w = 0; w < 4; w++) if (q + w >= sh && q + w < end) dst[q + w] = buf[q + w];
+    }
+  }
+}
+// cap: 0 = msm_bin_sort_kernel, else the staged kernel with that threshold (dynamic LDS above 64 KiB has to be allowed once per function and device)
+static hipError_t msm_bin_sort_launch(hipStream_t st, uint32_t nbins, uint32_t cap, const uint64_t* entries, const uint32_t* bin_base,
+                                      uint32_t* sorted_idx, uint32_t* off) {
+  if (!cap) {
+    hipLaunchKernelGGL(msm_bin_sort_kernel, dim3(nbins), dim3(256), 0, st, entries, bin_base, sorted_idx, off);
+    return hipSuccess;
+  }
+  static std::atomic<uint64_t> allowed{0};  // bit d: done on device d
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  const uint64_t bit = 1ull << (dev & 63);
+  if (!(allowed.load(std::memory_order_relaxed) & bit)) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_bin_sort_staged_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)msm_bin_stage_lds_bytes());
+    if (e != hipSuccess) return e;
+    allowed.fetch_or(bit, std::memory_order_relaxed);
+  }
+  hipLaunchKernelGGL(msm_bin_sort_staged_kernel, dim3(nbins), dim3(MSM_BIN_STAGE_BLOCK), msm_bin_stage_lds_bytes(), st, entries, bin_base,
+                     sorted_idx, off, std::min(cap, MSM_BIN_STAGE_CAP));
+  return hipSuccess;
 }
 
 // ------------------------------------------------------------------------------------------------ scan (exclusive, u32)
@@ -1700,6 +1808,7 @@ struct MsmWorkspace {
   hipEvent_t lane_in = nullptr, lane_out = nullptr;  // sorted list ready -> lane; accumulation done -> this MSM's own stream
   const uint32_t* last_err_dev = nullptr;  // device word raised by the last MSM's digit pass when a scalar was not reduced (null: not checked)
   int cus = 0;                             // compute units of the device this workspace lives on (queried on first use)
+  int bin_stage = -1;                      // pcdhip_msm_set_bin_stage: -1 MSM_BIN_STAGE_CAP, 0 msm_bin_sort_kernel, else the staged bin sort's threshold
   hipError_t ensure(int slot, size_t bytes) {
     if (cap[slot] >= bytes) return hipSuccess;
     if (buf[slot]) { hipError_t e = hipFree(buf[slot]); if (e != hipSuccess) return e; buf[slot] = nullptr; cap[slot] = 0; }
@@ -1861,14 +1970,17 @@ hipError_t msm_run(MsmWorkspace& ws, hipStream_t st, const MsmBasesView& bv, con
   const bool use_slots = single_pass && (double)pl.nkeys * cap * 4.0 <= 1.5e9;
   // default: MSD partition through LDS (needs whole bins of 2^MSM_BIN_SHIFT keys and an LDS histogram per workgroup)
   const uint32_t nbins = pl.nkeys >> MSM_BIN_SHIFT;
-  const bool use_partition = (sort_mode == 0 || sort_mode == 3) && pl.c >= MSM_BIN_SHIFT && nbins >= 1 && nbins <= MSM_MAX_BINS && n >= 4096;
+  const bool use_partition = (sort_mode == 0 || sort_mode == 3 || sort_mode == 4) && pl.c >= MSM_BIN_SHIFT && nbins >= 1 && nbins <= MSM_MAX_BINS && n >= 4096;
   // its write pass: staged through LDS in tiles of stage_tile scalars, or (0: pcdhip_msm_set_sort 3, the knob, or no tile fits) direct
   uint32_t stage_tile = 0;
-  if (use_partition && sort_mode == 0) {
+  if (use_partition && sort_mode != 3) {
     const int knob = msm_coarse_tile_knob();
     stage_tile = knob == 0 ? 0u : msm_stage_tile(pl.W, nbins);
     while (knob > 0 && stage_tile > (uint32_t)knob) stage_tile >>= 1;
   }
+  // its per-bin sort: bins of at most bin_cap entries ordered in LDS from one read (0: pcdhip_msm_set_sort 4 or the knob, the two-read kernel)
+  const uint32_t bin_cap = sort_mode == 4 || msm_bin_stage_knob() == 0 ? 0u
+                           : ws.bin_stage < 0 ? MSM_BIN_STAGE_CAP : std::min<uint32_t>((uint32_t)ws.bin_stage, MSM_BIN_STAGE_CAP);
   uint32_t* slots = nullptr;
   if (use_slots) { PCD_HIP_TRY(ws.ensure(WS_SLOTS, (size_t)pl.nkeys * cap * 4)); slots = (uint32_t*)ws.buf[WS_SLOTS]; }
 
@@ -1925,7 +2037,7 @@ hipError_t msm_run(MsmWorkspace& ws, hipStream_t st, const MsmBasesView& bv, con
       hipLaunchKernelGGL((msm_coarse_kernel<NS, true>), dim3(tiles), dim3(256), (size_t)nbins * 4, st, scalars_dev, n, pl.c, pl.W, Wg, bv.n_total,
                          bv.offset, nbins, cursor, entries, ones_count, ones_idx, SBITS, err, bv.inf_bits);
     }
-    hipLaunchKernelGGL(msm_bin_sort_kernel, dim3(nbins), dim3(256), 0, st, entries, bin_base, sorted, off);
+    PCD_HIP_TRY(msm_bin_sort_launch(st, nbins, bin_cap, entries, bin_base, sorted, off));
     PCD_HIP_TRY(mark(3));
     src = {sorted, nullptr, ones_idx, nullptr, 0u, ones_key};
   } else {

@@ -44,7 +44,7 @@ while time.time() - t0 < budget:
         if rnd.random() < 0.2:
             k = rnd.randrange(n); sc[k] = 0; sc[k, 0] = 1
     pre = rnd.choice((-1, 0, 2, 3))
-    sort = rnd.randrange(3)
+    sort = rnd.choice((0, 1, 2, 4))  # (4: the partition sort of mode 0 with the two-read per-bin sort)
     acc = rnd.choice(((0, 0, 0), (1, 0, 0), (2, rnd.randrange(2, 300), rnd.randrange(0, 20)), (2, 0, 0)))
     want = co.to_affine(cid, grp, co.msm(cid, grp, pts, sc, inf=inf, nthreads=8))
     ctx.set_precompute(pre); ctx.msm_set_sort(sort); ctx.msm_set_accumulate(*acc)
