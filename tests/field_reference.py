@@ -1,7 +1,8 @@
 """TEST INFRASTRUCTURE ONLY: exact-integer references and the seeded case lists for the device field arithmetic (pcd_amd/csrc/fp.hip.h)
 and the lazily reduced addition steps (ec.hip.h), shared by tests/test_field_ops_host.py (host build of the templates, 128-bit column
-check on) and tests/test_gpu_field_ops.py (gfx950 build).  Plain Python integers throughout: no numpy arithmetic, and nothing here is
-another build of the code under test.
+check on) and tests/test_gpu_field_ops.py (gfx950 build); and for the lane-split towers and the group law in them, which exist in the
+gfx950 build only (tests/test_gpu_lanesplit_ops.py; the lists themselves are checked by tests/test_lanesplit_reference_host.py).  Plain
+Python integers throughout: no numpy arithmetic, and nothing here is another build of the code under test.
 
 The raw device image of a field element is N 28-bit limbs in 32-bit words (N = 11 for the 298-bit fields, 27 for the 753-bit ones);
 limbs 0 .. N-2 are below 2^28 and the top limb takes the rest of the value.  A residue x is held as x R' mod p (+ p), R' = 2^(28 N).
@@ -23,7 +24,7 @@ MASK = B - 1
  F_TO_ABI, F_ABI_ROUNDTRIP, F_TO_WORDS, F_WORDS_ROUNDTRIP, F_SIGNED_SUM) = range(19)
 L_MUL, L_DOT2, L_DOT4, L_SQR, L_SCALE_CARRY, L_CARRY, L_SUB0, L_SUB2, L_SHL = range(9)
 T_MUL, T_SQR, T_INV = range(3)
-S_MADD_LZ, S_MADD_X, S_MADD_X_PLAIN = range(3)
+S_MADD_LZ, S_MADD_X, S_MADD_X_PLAIN, S_MADD_JAC = range(4)
 
 
 class Fld:
@@ -381,21 +382,45 @@ def accumulator_of(cid, grp, pt, z):
 
 
 def affine_of(cid, grp, coords, inf):
-    """the affine point of a raw accumulator record, by Python integers: x = X / ZZ, y = Y / ZZZ"""
+    """the affine point of a raw accumulator record, by Python integers: x = X / ZZ, y = Y / ZZZ (four coordinates), or of a raw Jacobian
+    record: x = X / Z^2, y = Y / Z^3 (three)"""
     if inf:
         return None
     c = O.CURVES[cid]
     F, _ = c.group(grp)
     fld = FLD[O.FIELDS.index(c.fq)]
-    X, Y, ZZ, ZZZ = (raw_to_ext(fld, v) for v in coords)
+    if len(coords) == 3:
+        X, Y, Z = (raw_to_ext(fld, v) for v in coords)
+        ZZ = F.mul(Z, Z)
+        ZZZ = F.mul(ZZ, Z)
+    else:
+        X, Y, ZZ, ZZZ = (raw_to_ext(fld, v) for v in coords)
     return (F.mul(X, F.inv(ZZ)), F.mul(Y, F.inv(ZZZ)))
 
 
-def step_cases(cid, grp, lz, seed=3, n_base=2, chain=8):
-    """[(raw accumulator record, [q_0 .. q_chain] raw affine images, expected affine point after step 1, ... after the whole chain)]:
-    valid accumulators (x z^2, y z^3, z^2, z^3) with every coordinate lifted to the bottom and to the top representative of its band --
-    madd_lz's X: carried, below p or in [15p, 16p); every other coordinate c and c + p -- in all 16 combinations, against q = a generic
-    point, the accumulator's own point (doubling branch), its negative (infinity) and the infinity image; then `chain` generic steps"""
+def jacobian_of(cid, grp, pt, z):
+    """(X, Y, Z) = (x z^2, y z^3, z) as ext-tuples of residues"""
+    return accumulator_of(cid, grp, pt, z)[:2] + (z,)
+
+
+def lifted_record(fld, coords, lift, top=None):
+    """the raw record of coordinates (tuples of raw coefficients below p): coordinate j on its upper representative c + p where bit j of `lift`
+    is set (top[j] p where `top` names another band), every coefficient of it; then the identity flag 0"""
+    rec = []
+    for j, co in enumerate(coords):
+        k = ((top[j] if top else 1) if (lift >> j) & 1 else 0)
+        for cf in co:
+            rec += limbs(cf + k * fld.p, fld.N)
+    return rec + [0]
+
+
+def step_cases(cid, grp, lz, seed=3, n_base=2, chain=8, jac=False):
+    """[(raw accumulator record, [q_0 .. q_chain] raw affine images, expected affine point after step 1, ... after the whole chain, (kind, lift),
+    (the accumulator's affine point, its z, the affine q_0 .. q_chain))]:
+    valid accumulators (x z^2, y z^3, z^2, z^3) -- jac: Jacobian ones (x z^2, y z^3, z) -- with every coordinate lifted to the bottom and to
+    the top representative of its band -- madd_lz's X: carried, below p or in [15p, 16p); every other coordinate c and c + p -- in all 16 (8)
+    combinations, against q = a generic point, the accumulator's own point (doubling branch), its negative (infinity) and the infinity
+    image; then `chain` generic steps.  Last, the identity record (flag set) against a generic point and against the infinity image."""
     c = O.CURVES[cid]
     F, a = c.group(grp)
     fld = FLD[O.FIELDS.index(c.fq)]
@@ -404,25 +429,85 @@ def step_cases(cid, grp, lz, seed=3, n_base=2, chain=8):
     pts = small_points(cid, grp, n_base + chain + 1, seed)
     base, generic = pts[:n_base], pts[n_base:]
     aff_raw = lambda P: [0] * (2 * d * N) if P is None else [w for co in P for cf in co for w in limbs(fld.mont(cf), N)]
+    ncoord = 3 if jac else 4
     cases = []
+
+    def emit(rec, pt, z, q, tag):
+        qs = [q] + generic[1:1 + chain]
+        want1 = O.ec_add(F, a, pt, q)
+        want = want1
+        for g in qs[1:]:
+            want = O.ec_add(F, a, want, g)
+        cases.append((rec, [aff_raw(x) for x in qs], want1, want, tag, (pt, z, qs)))
     for pt in base:
         z = tuple(rnd.randrange(1, p) for _ in range(d))
-        coords = [ext_to_raw(fld, e) for e in accumulator_of(cid, grp, pt, z)]
-        for lift in range(16):
-            rec = []
-            for j, co in enumerate(coords):
-                up = (lift >> j) & 1
-                k = (15 if (lz and j == 0) else 1) * up
-                for cf in co:
-                    rec += limbs(cf + k * p, N)
-            rec.append(0)
+        coords = [ext_to_raw(fld, e) for e in (jacobian_of if jac else accumulator_of)(cid, grp, pt, z)]
+        for lift in range(1 << ncoord):
+            rec = lifted_record(fld, coords, lift, top=(15, 1, 1, 1) if lz else None)
             for kind, q in (("generic", generic[0]), ("same", pt), ("negative", O.ec_neg(F, pt)), ("infinity", None)):
-                qs = [q] + generic[1:1 + chain]
-                want1 = O.ec_add(F, a, pt, q)
-                want = want1
-                for g in qs[1:]:
-                    want = O.ec_add(F, a, want, g)
-                cases.append((rec, [aff_raw(x) for x in qs], want1, want, (kind, lift)))
+                emit(rec, pt, z, q, (kind, lift))
+    for kind, q in (("identity+generic", generic[0]), ("identity+infinity", None)):
+        emit([0] * (ncoord * d * N) + [1], None, None, q, (kind, 0))
+    return cases
+
+
+def jadd_cases(cid, grp, seed=6, n_base=2):
+    """[(raw Jacobian record of P, raw Jacobian record of Q, expected affine P + Q, (kind, lift), (P, zP, Q, zQ))] for EC::add: P and Q with
+    Z lifted independently (bits 0, 1 of `lift`) and X, Y of either lifted together (bits 2, 3), Q = a generic point, P itself and -P under
+    a DIFFERENT Z (the H = 0 branch through unequal coordinates); then the identity on the left, on the right and on both sides, as
+    the flagged record, as literal Z = 0 and as Z = p in every coefficient under arbitrary X, Y"""
+    c = O.CURVES[cid]
+    F, a = c.group(grp)
+    fld = FLD[O.FIELDS.index(c.fq)]
+    p, N, d = fld.p, fld.N, F.d
+    rnd = random.Random(6000 + 100 * seed + 10 * cid + grp)
+    pts = small_points(cid, grp, n_base + 1, seed + 1)
+    base, generic = pts[:n_base], pts[n_base]
+    rz = lambda: tuple(rnd.randrange(1, p) for _ in range(d))
+
+    def record(pt, z, lz_, lxy):
+        coords = [ext_to_raw(fld, e) for e in jacobian_of(cid, grp, pt, z)]
+        return lifted_record(fld, coords, (4 if lz_ else 0) | (3 if lxy else 0))
+
+    def identity(form):
+        if form == "flag":
+            return [0] * (3 * d * N) + [1]
+        xy = [w for _ in range(2 * d) for w in limbs(rnd.randrange(2 * p), N)]
+        return xy + [w for _ in range(d) for w in limbs(p if form == "Z=p" else 0, N)] + [0]
+    cases = []
+    for pt in base:
+        zp = rz()
+        for kind, q in (("generic", generic), ("same", pt), ("negative", O.ec_neg(F, pt))):
+            zq = rz()
+            assert zq != zp
+            for lift in range(16):
+                cases.append((record(pt, zp, lift & 1, lift & 4), record(q, zq, lift & 2, lift & 8), O.ec_add(F, a, pt, q), (kind, lift), (pt, zp, q, zq)))
+        for form in ("flag", "Z=0", "Z=p"):
+            for lift in range(2):
+                cases.append((identity(form), record(pt, zp, lift, lift), pt, ("identity left " + form, lift), (None, None, pt, zp)))
+                cases.append((record(pt, zp, lift, lift), identity(form), pt, ("identity right " + form, lift), (pt, zp, None, None)))
+            cases.append((identity(form), identity("flag" if form == "Z=p" else "Z=p"), None, ("identity both " + form, 0), (None, None, None, None)))
+    return cases
+
+
+def jac_unary_cases(cid, grp, seed=8, n_base=2):
+    """[(raw Jacobian record of P, P, (kind, lift), z)] for EC::dbl and x_to_jac(x_from(.)): every coordinate lifted, in all 8 combinations,
+    and the identity in its three forms"""
+    c = O.CURVES[cid]
+    F, _ = c.group(grp)
+    fld = FLD[O.FIELDS.index(c.fq)]
+    p, N, d = fld.p, fld.N, F.d
+    rnd = random.Random(8000 + 100 * seed + 10 * cid + grp)
+    cases = []
+    for pt in small_points(cid, grp, n_base, seed + 2):
+        z = tuple(rnd.randrange(1, p) for _ in range(d))
+        coords = [ext_to_raw(fld, e) for e in jacobian_of(cid, grp, pt, z)]
+        for lift in range(8):
+            cases.append((lifted_record(fld, coords, lift), pt, ("finite", lift), z))
+    xy = lambda: [w for _ in range(2 * d) for w in limbs(rnd.randrange(2 * p), N)]
+    cases.append(([0] * (3 * d * N) + [1], None, ("identity flag", 0), None))
+    cases.append((xy() + [0] * (d * N) + [0], None, ("identity Z=0", 0), None))
+    cases.append((xy() + [w for _ in range(d) for w in limbs(p, N)] + [0], None, ("identity Z=p", 0), None))
     return cases
 
 
@@ -613,26 +698,263 @@ def check_tower_op(be, fid, name):
     return len(cases)
 
 
+def record_point(cid, grp, fld, ws, W, ncoord, flags, want, tag, lz_x=False):
+    """one returned record -- ncoord coordinate images of W words at ws[0:], identity flags `flags` (one, or one per lane of the item: all
+    must agree) -- against the expected affine point: the flag exact, limbs normalised, every coefficient below 2p (madd_lz's X: carried,
+    below 16p), and the affine point equal by Python integers"""
+    N = fld.N
+    assert all(f in (0, 1) for f in flags) and len(set(flags)) == 1, ("identity flags", tag, flags)
+    assert flags[0] == int(want is None), ("identity flag", tag, flags[0])
+    if want is None:
+        return
+    coords = []
+    for j in range(ncoord):
+        co = []
+        for i in range(0, W, N):
+            words = ws[j * W + i:j * W + i + N]
+            if lz_x and j == 0:
+                words = signed(words)
+            assert is_normal(words), ("limb not normalised", tag, j)
+            v = unlimbs(words)
+            assert 0 <= v < (16 if (lz_x and j == 0) else 2) * fld.p, ("coordinate outside its band", tag, j)
+            co.append(v)
+        coords.append(tuple(co))
+    assert affine_of(cid, grp, coords, False) == want, ("wrong point", tag)
+
+
 def check_steps(be, cid, grp, op):
     """one addition step and the chain behind it from every lifted accumulator, against the affine group law in Python integers"""
     c = O.CURVES[cid]
     fld = FLD[O.FIELDS.index(c.fq)]
-    cases = step_cases(cid, grp, lz=(op == S_MADD_LZ))
-    W = (len(cases[0][0]) - 1) // 4
+    ncoord = 3 if op == S_MADD_JAC else 4
+    cases = step_cases(cid, grp, lz=(op == S_MADD_LZ), jac=(op == S_MADD_JAC))
+    W = (len(cases[0][0]) - 1) // ncoord
     for steps, idx in ((1, 2), (len(cases[0][1]), 3)):
         out = be.step(cid, grp, op, [rec for rec, *_ in cases], [[w for q in qs[:steps] for w in q] for _, qs, *_ in cases], steps)
         for case, ws in zip(cases, out):
-            coords = []
-            for j in range(4):
-                words = ws[j * W:(j + 1) * W]
-                if op == S_MADD_LZ and j == 0:
-                    words = signed(words)
-                coords.append(tuple(unlimbs(words[i:i + fld.N]) for i in range(0, W, fld.N)))
-            assert ws[4 * W] in (0, 1)
-            got = affine_of(cid, grp, coords, ws[4 * W] == 1)
-            assert got == case[idx], (cid, grp, op, steps, case[4])
-            if got is not None:    # the documented bands of the record the step leaves behind
-                for j, co in enumerate(coords):
-                    for v in co:
-                        assert 0 <= v < (16 if (op == S_MADD_LZ and j == 0) else 2) * fld.p, (cid, grp, op, steps, case[4], j)
+            record_point(cid, grp, fld, ws, W, ncoord, ws[ncoord * W:], case[idx], (cid, grp, op, steps, case[4]), lz_x=(op == S_MADD_LZ))
     return len(cases)
+
+
+# ----------------------------------------------------------------------------- lane-split towers and the group law in them (gfx950 only)
+# type / group numbers and operation numbers of tests/gpucheck/lanesplit_check.hip; the coordinate field of split group g is split type g
+SPLIT_NAMES = ["Fp2S-298A", "Fp3S-298B", "Fp2S-753A", "Fp3S-753B", "Fp2S-753A-mailbox", "Fp3S-753B-mailbox"]
+SPLIT_TOWER_OPS = ["mul", "sqr", "add", "sub", "neg", "dbl", "mul_small", "mul_by_a", "is_zero", "is_raw_zero", "eq", "one", "from_abi",
+                   "abi_roundtrip"]
+SPLIT_GROUP_OPS = ["S_MADD_X", "S_MADD_JAC", "J_ADD", "J_DBL", "X_ROUNDTRIP"]
+
+
+def split_curve(sid):
+    """the curve (= base field) number of a split type / group: 0 .. 3 plain, 4 / 5 the mailbox forms over fields 2 / 3"""
+    return sid if sid < 4 else sid - 2
+
+
+def split_zero_cases(fid, seed=9):
+    """[(a, b)] for is_zero / is_raw_zero / ==: exactly ONE coefficient 0 or p and the others not; the same element on the other
+    representative of every coefficient; pairs that differ in one coefficient only and pairs that agree in one only; every coefficient
+    but one zero; and every mix of the representatives 0 and p (the zero element)"""
+    p = FLD[fid].p
+    d, _ = tower_of(fid)
+    rnd = random.Random(9000 + 10 * seed + fid)
+    nz = lambda: rnd.choice([1, p - 1, p + 1, 2 * p - 1, rnd.randrange(2, p - 1), rnd.randrange(p + 2, 2 * p - 1)])
+    other = lambda c: c + p if c < p else c - p
+    cases = []
+    for j in range(d):
+        for z in (0, p):
+            a = tuple(z if i == j else nz() for i in range(d))
+            cases.append((a, a))
+            cases.append((a, tuple(other(c) for c in a)))
+            b = list(a)
+            while (b[j] - a[j]) % p == 0:
+                b[j] = nz()
+            cases.append((a, tuple(b)))                                                     # differ in coefficient j only
+            cases.append((a, tuple(a[i] if i == j else (a[i] + 1) % (2 * p) for i in range(d))))   # agree in coefficient j only
+            cases.append((tuple(nz() if i == j else rnd.choice((0, p)) for i in range(d)), a))     # every coefficient but j zero
+    for m in range(1 << d):
+        zero = tuple(p if (m >> i) & 1 else 0 for i in range(d))
+        cases.append((zero, tuple(p - c for c in zero)))
+    return cases
+
+
+def split_tower_cases(fid):
+    """tower_cases (100 pairs, every coefficient drawn independently from the operand classes) and split_zero_cases"""
+    return tower_cases(fid) + split_zero_cases(fid)
+
+
+def split_masks(n, seed=11):
+    """the three active-item masks every case list runs under: all items, every third item inactive, a seeded random half inactive"""
+    rnd = random.Random(seed + n)
+    half = [1] * n
+    for i in rnd.sample(range(n), n // 2):
+        half[i] = 0
+    return [("all", [1] * n), ("every third off", [0 if i % 3 == 2 else 1 for i in range(n)]), ("random half off", half)]
+
+
+class SplitBackend:
+    """ctypes entry points of tests/gpucheck/libgpucheck_ls.so"""
+
+    def __init__(self, lib):
+        import ctypes as C
+        self.C, self.lib = C, lib
+        vp, i, u = C.c_void_p, C.c_int, C.c_uint32
+        lib.gc_split_tower_ops.argtypes = [i, i, vp, vp, u, i, vp, vp, vp]
+        lib.gc_split_group_ops.argtypes = [i, i, vp, vp, i, i, vp, vp, vp]
+        lib.gc_split_words.argtypes = [i, i, i, i, vp]
+        lib.gc_split_sentinel.restype = u
+        self.sentinel = int(lib.gc_split_sentinel())
+
+    def _call(self, what, sid, op, a_rows, b_rows, mid, active):
+        """one launch: rows of the ACTIVE items as lists of words, None for the inactive ones.  Checked here: the harness's own word counts
+        against the rows passed, `ran` = lanes per item times active items, every word of an inactive item still the sentinel"""
+        import numpy as np
+        n = len(a_rows)
+        assert n == len(b_rows) == len(active) and n > 0
+        w3 = np.zeros(3, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data_as(self.C.c_void_p)
+        assert self.lib.gc_split_words(what, sid, op, mid if what == 1 else 0, ptr(w3)) == 0
+        wa, wb, wo = (int(x) for x in w3)
+        arrs = []
+        for rows, w in ((a_rows, wa), (b_rows, wb)):
+            assert all(len(r) == w for r in rows), ("operand words", w, [len(r) for r in rows][:3])
+            arrs.append(np.ascontiguousarray(np.array(rows, dtype=np.int64).astype(np.uint32).reshape(-1)))
+            assert arrs[-1].size == n * w
+        act = np.ascontiguousarray(np.array(active, dtype=np.uint8))
+        out = np.zeros(n * wo + 1, dtype=np.uint32)
+        ran = np.zeros(1, dtype=np.uint32)
+        fn = self.lib.gc_split_tower_ops if what == 0 else self.lib.gc_split_group_ops
+        rc = fn(sid, op, ptr(arrs[0]), ptr(arrs[1]), mid, n, ptr(act), ptr(out), ptr(ran))
+        assert rc == 0, ("harness error", rc)
+        L = 2 + split_curve(sid) % 2
+        assert int(ran[0]) == L * sum(active), ("lanes run", int(ran[0]), "of", L * sum(active))
+        rows = []
+        for i in range(n):
+            ws = [int(w) for w in out[i * wo:(i + 1) * wo]]
+            if active[i]:
+                rows.append(ws)
+            else:
+                assert all(w == self.sentinel for w in ws), ("inactive item written", i)
+                rows.append(None)
+        return rows
+
+    def tower(self, sid, op, a_rows, b_rows, k, active):
+        return self._call(0, sid, op, a_rows, b_rows, k, active)
+
+    def group(self, sid, op, p_rows, q_rows, steps, active):
+        return self._call(1, sid, op, p_rows, q_rows, steps, active)
+
+
+def _mask_runs(cases):
+    """(label, case list, active flags): the whole list under the three masks, then its first item alone (one item, L active lanes in a
+    partly filled wave: the shape of the single-item kernels)"""
+    return [(lbl, cases, act) for lbl, act in split_masks(len(cases))] + [("one item", cases[:1], [1])]
+
+
+def abi_words(fld, x):
+    """the C-ABI image of the residue x: x R mod p (R = 2^(32 n32)), n32 little-endian 32-bit words"""
+    v = x * fld.R_abi % fld.p
+    return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(fld.n32)]
+
+
+def check_split_tower_op(sb, sid, name):
+    """every case of one operation of one lane-split type, under every mask, against Python integers; returns the number of items checked"""
+    fid = split_curve(sid)
+    fld = FLD[fid]
+    p, N = fld.p, fld.N
+    d, nr = tower_of(fid)
+    curve = O.CURVES[fid]
+    assert curve.fq is O.FIELDS[fid]
+    E = O.Ext(p, d, nr)
+    op = SPLIT_TOWER_OPS.index(name)
+    flat = lambda e: [w for c in e for w in limbs(c, N)]
+    pad = lambda ws: ws + [0] * (d * N - len(ws))
+    checked = 0
+    for k in (small_constants(fid) if name == "mul_small" else [0]):
+        for lbl, cases, active in _mask_runs(split_tower_cases(fid)):
+            if name in ("from_abi", "abi_roundtrip"):
+                a_rows = [pad([w for c in a for w in abi_words(fld, c % p)]) for a, _ in cases]
+            else:
+                a_rows = [flat(a) for a, _ in cases]
+            out = sb.tower(sid, op, a_rows, [flat(b) for _, b in cases], k, active)
+            for (a, b), row, ws in zip(cases, a_rows, out):
+                if ws is None:
+                    continue
+                what = (SPLIT_NAMES[sid], name, k, lbl, a, b)
+                co = [ws[j * N:(j + 1) * N] for j in range(d)]
+                if name in ("is_zero", "is_raw_zero", "eq"):
+                    want = {"is_zero": all(c % p == 0 for c in a), "is_raw_zero": all(c == 0 for c in a),
+                            "eq": all((x - y) % p == 0 for x, y in zip(a, b))}[name]
+                    for j in range(d):   # every lane of the item reports, and all agree
+                        assert co[j][0] == int(want), (what, "lane", j)
+                        if name == "eq":
+                            assert co[j][1] == int(not want), (what, "lane", j, "!=")
+                elif name == "abi_roundtrip":
+                    assert ws[:d * fld.n32] == row[:d * fld.n32], what
+                    assert all(w == sb.sentinel for w in ws[d * fld.n32:]), what
+                else:
+                    x, y = raw_to_ext(fld, a), raw_to_ext(fld, b)
+                    if name == "mul":
+                        want = [fld.mont(c) for c in E.mul(x, y)]
+                    elif name == "sqr":
+                        want = [fld.mont(c) for c in E.mul(x, x)]
+                    elif name == "mul_by_a":   # the twist coefficient of the curve itself: (a nr, 0) in Fq2, (0, 0, a) = a u^2 in Fq3
+                        want = list(E.mul(tuple(c % p for c in a), curve.a2))
+                    elif name == "one":
+                        want = [fld.R] + [0] * (d - 1)
+                    elif name == "from_abi":
+                        want = [fld.mont(c % p) for c in a]   # the C-ABI image was that of the residue a_j mod p
+                    else:
+                        want = {"add": [x_ + y_ for x_, y_ in zip(a, b)], "sub": [x_ - y_ for x_, y_ in zip(a, b)], "neg": [-x_ for x_ in a],
+                                "dbl": [2 * x_ for x_ in a], "mul_small": [k * x_ for x_ in a]}[name]
+                    for j in range(d):
+                        check_reduced(fld, co[j], want[j], (what, "coefficient", j))
+                checked += 1
+    return checked
+
+
+def split_group_cases(sid, name):
+    """the case list of one group operation in one lane-split group: rows p, q of the harness, expected affine points, tags"""
+    cid = split_curve(sid)
+    if name in ("S_MADD_X", "S_MADD_JAC"):
+        return step_cases(cid, 2, lz=False, jac=(name == "S_MADD_JAC"))
+    if name == "J_ADD":
+        return jadd_cases(cid, 2)
+    return jac_unary_cases(cid, 2)
+
+
+def check_split_group_op(sb, sid, name):
+    """every case of one group operation in one lane-split group, under every mask, against the affine group law in Python integers;
+    returns the number of items checked"""
+    cid = split_curve(sid)
+    c = O.CURVES[cid]
+    F, a = c.group(2)
+    fld = FLD[O.FIELDS.index(c.fq)]
+    W = F.d * fld.N
+    L = F.d
+    op = SPLIT_GROUP_OPS.index(name)
+    all_cases = split_group_cases(sid, name)
+    chain = name in ("S_MADD_X", "S_MADD_JAC")
+    ncoord = 4 if name == "S_MADD_X" else 3
+    checked = 0
+    for steps, idx in (((1, 2), (len(all_cases[0][1]), 3)) if chain else ((0, None),)):
+        for lbl, cases, active in _mask_runs(all_cases):
+            if chain:
+                q_rows = [[w for q in case[1][:steps] for w in q] for case in cases]
+            elif name == "J_ADD":
+                q_rows = [case[1] for case in cases]
+            else:
+                q_rows = [[] for _ in cases]
+            out = sb.group(sid, op, [case[0] for case in cases], q_rows, steps, active)
+            for case, ws in zip(cases, out):
+                if ws is None:
+                    continue
+                if chain:
+                    want, tag = case[idx], case[4]
+                elif name == "J_ADD":
+                    want, tag = case[2], case[3]
+                else:
+                    want, tag = (O.ec_add(F, a, case[1], case[1]) if name == "J_DBL" else case[1]), case[2]
+                record_point(cid, 2, fld, ws, W, ncoord, ws[4 * W:4 * W + L], want, (SPLIT_NAMES[sid], name, steps, lbl, tag))
+                if ncoord == 3:
+                    assert all(w == sb.sentinel for w in ws[3 * W:4 * W]), ("fourth slot written", SPLIT_NAMES[sid], name, tag)
+                checked += 1
+    return checked

@@ -4,11 +4,12 @@
 // build; the expected values are Python integers (tests/field_reference.py).  Every kernel counts the elements it processed in `ran`.
 // variant: 0 the inlined products (all fields), 1 the non-inlined mul_call / sqr_call bodies, 2 the LDS mailbox form (753-bit fields).
 // Built by __graft_entry__.build() (hipcc, gfx950) into tests/gpucheck/libgpucheck_fp.so; tests/test_gpu_field_ops.py drives it.
-// One source, four translation units (-DFIELDOPS_PART=0..3, tests/gpucheck/Makefile) so that they compile side by side: 0 the 298-bit fields,
-// their Lz family and towers; 1 / 2 the three variants and the tower of the 753-bit fields A / B; 3 the accumulator steps.
+// One source, five translation units (-DFIELDOPS_PART=0..4, tests/gpucheck/Makefile) so that they compile side by side: 0 the 298-bit fields,
+// their Lz family and towers; 1 / 2 the three variants and the tower of the 753-bit fields A / B; 3 the accumulator steps of the 298-bit
+// groups; 4 those of the 753-bit G1 groups in their mailbox form.
 #include "fieldops_ops.h"
 #ifndef FIELDOPS_PART
-#error "compile with -DFIELDOPS_PART=0..3"
+#error "compile with -DFIELDOPS_PART=0..4"
 #endif
 using namespace pcd;
 using namespace fieldops;
@@ -38,7 +39,7 @@ template <class G>
 __global__ void __launch_bounds__(64) step_kernel(int op, const uint32_t* acc, const uint32_t* q, int steps, int n, uint32_t* out, uint32_t* ran) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= n) return;
-  madd_steps<G>(op, acc + (size_t)i * step_words<G>(), q + (size_t)i * steps * 2 * G::F::WORDS, steps, out + (size_t)i * step_words<G>());
+  madd_steps<G>(op, acc + (size_t)i * step_words<G>(op), q + (size_t)i * steps * 2 * G::F::WORDS, steps, out + (size_t)i * step_words<G>(op));
   atomicAdd(ran, 1u);
 }
 
@@ -85,7 +86,8 @@ static int run_tower(int op, const uint32_t* a, const uint32_t* b, int n, uint32
 template <class G>
 static int run_step(int op, const uint32_t* acc, const uint32_t* q, int steps, int n, uint32_t* out, uint32_t* ran) {
   if (op == S_MADD_LZ && !LazyCapable<typename G::F>::value) return -1;
-  Run r(acc, (size_t)n * step_words<G>(), q, (size_t)n * steps * 2 * G::F::WORDS, (size_t)n * step_words<G>());
+  if (op == fieldops::S_MADD_JAC && G::F::Base::INLINE_ARITH) return -1;
+  Run r(acc, (size_t)n * step_words<G>(op), q, (size_t)n * steps * 2 * G::F::WORDS, (size_t)n * step_words<G>(op));
   if (r.ok) hipLaunchKernelGGL((step_kernel<G>), blocks(n), dim3(64), 0, 0, op, r.a, r.b, steps, n, r.out, r.ran);
   return r.finish(out, ran);
 }
@@ -93,6 +95,7 @@ static int run_step(int op, const uint32_t* acc, const uint32_t* q, int steps, i
 // the parts' entry points, each defined in one translation unit
 int fo_field_753(int field, int variant, int op, const uint32_t* a, const uint32_t* b, uint32_t k, int n, uint32_t* out, uint32_t* ran);
 int fo_tower_753(int field, int op, const uint32_t* a, const uint32_t* b, int n, uint32_t* out, uint32_t* ran);
+int fo_step_753(int curve, int op, const uint32_t* acc, const uint32_t* q, int steps, int n, uint32_t* out, uint32_t* ran);
 
 #if FIELDOPS_PART == 0
 extern "C" int gc_field_ops(int field, int variant, int op, const uint32_t* a, const uint32_t* b, uint32_t k, int n, uint32_t* out, uint32_t* ran) {
@@ -141,7 +144,7 @@ int fo_field_753b(int variant, int op, const uint32_t* a, const uint32_t* b, uin
 }
 int fo_tower_753b(int op, const uint32_t* a, const uint32_t* b, int n, uint32_t* out, uint32_t* ran) { return run_tower<PartT>(op, a, b, n, out, ran); }
 #endif
-#else
+#elif FIELDOPS_PART == 3
 extern "C" int gc_madd_step(int curve, int grp, int op, const uint32_t* acc, const uint32_t* q, int steps, int n, uint32_t* out, uint32_t* ran) {
   if (n <= 0 || steps <= 0 || op < 0 || op >= S_OPS) return -1;
   switch (curve * 2 + grp - 1) {
@@ -149,7 +152,14 @@ extern "C" int gc_madd_step(int curve, int grp, int op, const uint32_t* acc, con
     case 1: return run_step<G2_MNT4_298>(op, acc, q, steps, n, out, ran);
     case 2: return run_step<G1_MNT6_298>(op, acc, q, steps, n, out, ran);
     case 3: return run_step<G2_MNT6_298>(op, acc, q, steps, n, out, ran);
+    case 4: case 6: return op == S_MADD_JAC || op == S_MADD_X_PLAIN ? fo_step_753(curve, op, acc, q, steps, n, out, ran) : -1;
     default: return -1;
   }
+}
+#else
+// the 27-limb G1 groups in the mailbox form their accumulation runs (ec.hip.h AccOf): EC::madd on a Jacobian record, and madd_x_plain (PCD_XYZZ_753)
+int fo_step_753(int curve, int op, const uint32_t* acc, const uint32_t* q, int steps, int n, uint32_t* out, uint32_t* ran) {
+  if (curve == 2) return run_step<G1CfgMB<F753A, F753B, PCD_MNT4_753_A_SMALL, 2>>(op, acc, q, steps, n, out, ran);
+  return run_step<G1CfgMB<F753B, F753A, PCD_MNT6_753_A_SMALL, 3>>(op, acc, q, steps, n, out, ran);
 }
 #endif

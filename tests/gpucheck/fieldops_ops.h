@@ -14,7 +14,7 @@ enum FieldOp {
 };
 enum LzOp { L_MUL = 0, L_DOT2, L_DOT4, L_SQR, L_SCALE_CARRY, L_CARRY, L_SUB0, L_SUB2, L_SHL, L_OPS };
 enum TowerOp { T_MUL = 0, T_SQR, T_INV, T_OPS };
-enum StepOp { S_MADD_LZ = 0, S_MADD_X, S_MADD_X_PLAIN, S_OPS };
+enum StepOp { S_MADD_LZ = 0, S_MADD_X, S_MADD_X_PLAIN, S_MADD_JAC, S_OPS };
 constexpr int SIGNED_SUM_MAX_TERMS = 16;
 
 // words per element of the operands: a, b (F_SIGNED_SUM: k terms of N words, and k int32 coefficients); the result is always N words
@@ -122,7 +122,8 @@ PCD_HD void tower_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* out
 }
 
 // One accumulator record: X || Y || ZZ || ZZZ (raw images) || identity flag; `steps` mixed additions of the affine points q[0 .. steps).
-template <class G> constexpr int step_words() { return 4 * G::F::WORDS + 1; }
+// S_MADD_JAC: the Jacobian record X || Y || Z || identity flag of EC::madd (what the 27-limb G1 / Fq3 groups accumulate in).
+template <class G> PCD_HD int step_words(int op) { return (op == S_MADD_JAC ? 3 : 4) * G::F::WORDS + 1; }
 template <class G>
 PCD_HD void madd_steps(int op, const uint32_t* acc, const uint32_t* q, int steps, uint32_t* out) {
   typedef typename G::F F;
@@ -136,6 +137,15 @@ PCD_HD void madd_steps(int op, const uint32_t* acc, const uint32_t* q, int steps
       for (int s = 0; s < steps; s++) a = E::madd_lz(a, Aff<F>::load(q + (size_t)s * 2 * W));
       for (int i = 0; i < W; i++) out[i] = (uint32_t)a.X.v[i];
       a.Y.store(out + W); a.ZZ.store(out + 2 * W); a.ZZZ.store(out + 3 * W); out[4 * W] = a.inf ? 1u : 0u;
+    }
+    return;
+  }
+  if (op == S_MADD_JAC) {   // (only the groups with non-inlined arithmetic accumulate in Jacobian coordinates: msm.hip.h MsmUseXyzz)
+    if constexpr (!F::Base::INLINE_ARITH) {
+      Jac<F> a = Jac<F>::load(acc);
+      if (acc[3 * W] != 0) a = Jac<F>::infinity();
+      for (int s = 0; s < steps; s++) a = E::madd(a, Aff<F>::load(q + (size_t)s * 2 * W));
+      a.store(out); out[3 * W] = a.is_inf() ? 1u : 0u;
     }
     return;
   }

@@ -194,11 +194,12 @@ extern "C" int hc_tower_ops(int field, int op, const uint32_t* a, const uint32_t
   }
   return 0;
 }
-// `steps` mixed additions per element from a raw accumulator record (X || Y || ZZ || ZZZ || identity flag), points q[element][step]
+// `steps` mixed additions per element from a raw accumulator record (X || Y || ZZ || ZZZ || identity flag; S_MADD_JAC: X || Y || Z || flag), points q[element][step]
 template <class G>
 static int madd_step(int op, const uint32_t* acc, const uint32_t* q, int steps, int n, uint32_t* out, uint32_t* ran) {
   if (op == fieldops::S_MADD_LZ && !LazyCapable<typename G::F>::value) return -1;
-  constexpr int SW = fieldops::step_words<G>(), QW = 2 * G::F::WORDS;
+  if (op == fieldops::S_MADD_JAC && G::F::Base::INLINE_ARITH) return -1;
+  const int SW = fieldops::step_words<G>(op), QW = 2 * G::F::WORDS;
   for (int i = 0; i < n; i++) { fieldops::madd_steps<G>(op, acc + (size_t)i * SW, q + (size_t)i * steps * QW, steps, out + (size_t)i * SW); ++*ran; }
   return 0;
 }

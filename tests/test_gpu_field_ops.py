@@ -57,15 +57,32 @@ def test_tower_op(be, fid, name):
     assert fr.check_tower_op(be, fid, name) > 0
 
 
-# madd_lz: G1 of curves 0 and 1.  madd_x (what the accumulation calls): on curve 0 G2 is Fq2 and madd_x IS madd_x_lz2 -- the only place the
-# product has it (LazyFq2 exists for Fp2 alone); on curve 1 G2 is Fq3 and madd_x is madd_x_plain.  madd_x_plain on G1 and on curve 0's G2
-# for comparison.  Not covered: EC::madd_lz_st, the LDS-resident form of madd_lz behind PCD_ACC_LDS (an experiment, off by default).
+# Which types the kernels instantiate (ec.hip.h AccOf / SplitOfTail, msm.hip.h MsmUseXyzz), and where each is compared with integers:
+#   madd_lz: the accumulation of G1 on curves 0 and 1.                                             here
+#   madd_x = madd_x_lz2 on the unsplit Fq2 of curve 0 (LazyFq2 exists for Fp2 alone): its G2 accumulation.   here
+#   curve 1's G2 (Fq3) accumulates with madd_x_plain in the LANE-SPLIT G2Cfg3S<F298B, .., true>, three lanes per point: the kernels never
+#   instantiate the unsplit G2_MNT6_298 that "madd_x(plain)-c1-G2-Fq3" runs.  That case stays as a check of the formula on the unsplit
+#   tower; its split counterpart is test_split_fq3_accumulation_step below (tests/gpucheck/lanesplit_check.hip), and all the lane-split
+#   groups, plain and mailbox, are in tests/test_gpu_lanesplit_ops.py.
+#   G1 of curves 2 and 3 accumulates with EC<G1CfgMB>::madd on a Jacobian record (mailbox field): madd-c2-G1-mailbox, madd-c3-G1-mailbox;
+#   madd_x_plain in the same type is the PCD_XYZZ_753 form.
+#   madd_x_plain on G1 of curves 0 / 1 and on curve 0's unsplit G2: for comparison.
+# Not covered: EC::madd_lz_st, the LDS-resident form of madd_lz behind PCD_ACC_LDS (an experiment, off by default).
 STEP_CASES = [pytest.param(0, 1, fr.S_MADD_LZ, id="madd_lz-c0-G1"), pytest.param(1, 1, fr.S_MADD_LZ, id="madd_lz-c1-G1"),
               pytest.param(0, 2, fr.S_MADD_X, id="madd_x_lz2-c0-G2"), pytest.param(1, 2, fr.S_MADD_X, id="madd_x(plain)-c1-G2-Fq3"),
               pytest.param(0, 1, fr.S_MADD_X_PLAIN, id="madd_x_plain-c0-G1"), pytest.param(1, 1, fr.S_MADD_X_PLAIN, id="madd_x_plain-c1-G1"),
-              pytest.param(0, 2, fr.S_MADD_X_PLAIN, id="madd_x_plain-c0-G2")]
+              pytest.param(0, 2, fr.S_MADD_X_PLAIN, id="madd_x_plain-c0-G2"),
+              pytest.param(2, 1, fr.S_MADD_JAC, id="madd-c2-G1-mailbox"), pytest.param(3, 1, fr.S_MADD_JAC, id="madd-c3-G1-mailbox"),
+              pytest.param(2, 1, fr.S_MADD_X_PLAIN, id="madd_x_plain-c2-G1-mailbox"),
+              pytest.param(3, 1, fr.S_MADD_X_PLAIN, id="madd_x_plain-c3-G1-mailbox")]
 
 
 @pytest.mark.parametrize("cid,grp,op", STEP_CASES)
 def test_accumulator_step_from_lifted_coordinates(be, cid, grp, op):
     assert fr.check_steps(be, cid, grp, op) > 0
+
+
+def test_split_fq3_accumulation_step():
+    """the split counterpart of madd_x(plain)-c1-G2-Fq3: the same case list in G2Cfg3S<F298B, .., true>, the type the kernels run"""
+    import test_gpu_lanesplit_ops as ls
+    assert fr.check_split_group_op(fr.SplitBackend(ls._lib()), 1, "S_MADD_X") > 0
