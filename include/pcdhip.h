@@ -608,6 +608,67 @@ int pcdhip_marlin_sumcheck_f(pcdhip_ctx* ctx, const uint64_t* alpha_mont, const 
                              const pcdhip_buf* const row_col[3] /* array or entries nullable */, const pcdhip_buf* const val[3], size_t n,
                              pcdhip_buf* f_out);
 
+/* ---- K10 Marlin's index on device: arithmetise A, B, C onto K and B, commit ----------------------------------------------------
+ * The producer of what K9 consumes: ark-marlin's `index` turns each constraint matrix into the polynomials row, col, row_col and val
+ * -- by their evaluations on a domain K of at least nnz elements, their coefficients, and their evaluations on the larger domain B
+ * that round 3 divides on -- and commits to the twelve.  Same conventions as K8 / K9: device vectors of ABI Montgomery elements of ONE
+ * scalar field, the context's own stream and workspaces, device 0 of a multi-device context, PCDHIP_E_ARG for bad arguments, no
+ * randomness, no CPU fallback.
+ *
+ * The arithmetisation of one matrix M with entries (r, c, v), w the generator of the resident transform of domain_h_n elements and pi
+ * the `reindex_by_subdomain` of pcdhip_marlin_mats_upload.  Entry k runs over M row by row; inside a row by ascending column index,
+ * equal columns in the order the CSR gives them (upstream sorts a row stably when it is not ascending); duplicate (r, c) entries stay
+ * separate entries and explicit zeros stay entries.  This order is part of the contract: the commitments depend on it.
+ *   k < nnz_M:          row_k = w^pi(c)    col_k = w^r    val_k = v w^pi(c) / |H|    row_col_k = row_k col_k
+ *   nnz_M <= k < |K|:   row_k = col_k = row_col_k = 1,   val_k = 0
+ * (val_k is v / u_H(w^pi(c), w^pi(c)) in closed form: u_H(x, x) = |H| x^(|H| - 1) = |H| / x on H.)
+ * Domains: |K| = pcdhip_domain_size(field, max(nnz_A, nnz_B, nnz_C, 1)) and |B| = pcdhip_domain_size(field, max(3 |K| - 3, 1)).  The
+ * rule for |B| is upstream's RESTATED FROM MEMORY (ark-marlin is not vendored here: the domain on which the prover divides a - b f by
+ * v_K, whose degree is below 3 |K| - 3); a caller that knows better passes its own sizes.
+ *
+ * pcdhip_marlin_index_build: validates as pcdhip_marlin_mats_upload does (domain sizes, domain_x_n divides domain_h_n, equal row
+ * counts, rows and num_cols <= domain_h_n, column indices below num_cols), lays every row out in ascending column order on the host
+ * (O(nnz), once per index), uploads the three CSRs, and then works on the device alone: ONE launch writes the twelve vectors on K (one
+ * lane per k and matrix: its row from the row pointers, pi(c) in the lane, w^j from the transform's resident powers), twelve inverse
+ * transforms on K give the coefficients, and each coefficient vector, zero-padded on the device to |B| elements, goes through a forward
+ * transform on B -- so on B row_col is the interpolated polynomial's evaluation, NOT row col.  Transforms are the library's general
+ * ones: K and B may be mixed-radix.  domain_k_n / domain_b_n: 0 for the rules above, or the caller's own sizes -- each n = 2^a q^b that
+ * pcdhip_fft_general takes, domain_k_n >= the largest nnz, domain_b_n >= domain_k_n; PCDHIP_E_ARG otherwise, and
+ * PCDHIP_E_SIZE_UNSUPPORTED when a rule finds no domain of the size it needs.  keep: bit 0 the coefficients on K, bit 1 the evaluations
+ * on K, bit 2 the evaluations on B; 0 means all three.  Forms that keep leaves out are computed where a kept one needs them and hold
+ * no memory once the call returns.  The call waits for its own uploads: it never returns while reading caller memory. */
+typedef struct pcdhip_marlin_index pcdhip_marlin_index;
+int pcdhip_marlin_index_build(pcdhip_ctx* ctx, int field_id, const pcdhip_csr* A, const pcdhip_csr* B, const pcdhip_csr* C, size_t num_cols,
+                              size_t domain_h_n, size_t domain_x_n, size_t domain_k_n /* 0: rule */, size_t domain_b_n /* 0: rule */,
+                              int keep, pcdhip_marlin_index** out);
+void pcdhip_marlin_index_free(pcdhip_ctx* ctx, pcdhip_marlin_index* index);
+/* out[0] = |K|, out[1] = |B|, out[2] = the largest nnz of the three matrices, out[3] = device bytes the handle holds */
+int pcdhip_marlin_index_info(const pcdhip_marlin_index* index, uint64_t out[4]);
+/* Device time of the build that made this handle, from events on the context's stream, in milliseconds: out_ms[0] the arithmetisation
+ * launch, out_ms[1] the twelve inverse transforms on K with their conversions, out_ms[2] the twelve extensions to B (zero tail, forward
+ * transform, conversion); a part that keep left out is 0 */
+int pcdhip_marlin_index_timings(const pcdhip_marlin_index* index, float out_ms[3]);
+/* One vector of the index as a BORROWED pcdhip_buf: valid until the index is freed, not to be freed or written by the caller.  form 0
+ * coefficients (|K| of them) / 1 evaluations on K / 2 evaluations on B; matrix 0..2 = A, B, C; poly 0..3 = row, col, row_col, val.
+ * PCDHIP_E_ARG for an index out of range and for a form that was not kept.  The buffers are ordinary device vectors: pcdhip_marlin_sumcheck_ab
+ * / _f take them as row[3], col[3], row_col[3], val[3]; pcdhip_kzg_commit items, pcdhip_poly_eval and pcdhip_buf_download take them too. */
+int pcdhip_marlin_index_vec(const pcdhip_marlin_index* index, int form, int matrix, int poly, const pcdhip_buf** out);
+/* The twelve index commitments, matrix-major (A.row, A.col, A.row_col, A.val, B.row, ...): pcdhip_kzg_commit over the coefficient form,
+ * non-hiding and without degree bounds, as upstream commits the index.  comm_xy: 12 affine points, comm_inf: 12 flags.  Argument rules
+ * of pcdhip_kzg_commit (powers_of_g of the curve whose scalar field the index is over, at least as many as the longest trimmed
+ * polynomial, not sharded, no outstanding MSM tickets); PCDHIP_E_ARG also when the coefficient form was not kept. */
+int pcdhip_marlin_index_commit(pcdhip_ctx* ctx, const pcdhip_marlin_index* index, const pcdhip_bases* powers_of_g, uint64_t* comm_xy,
+                               uint8_t* comm_inf);
+/* Two device entry points the builder is made of, which the rounds need as well (f on K -> coefficients -> f on B is the same step).
+ * pcdhip_fft_general_dev: pcdhip_fft_general on a device vector, in place -- any n = 2^a q^b (b = 0: pcdhip_fft_dev), n <= data's
+ * elements; PCDHIP_E_SIZE_UNSUPPORTED for another n.
+ * pcdhip_poly_evals_on_domain: out = the transform (coset != 0: on the coset) of the polynomial p of `len` coefficients over the domain
+ * of domain_n elements, p padded with zeros: ark-poly `evaluate_over_domain`.  len <= domain_n <= out's elements and len <= p's
+ * (PCDHIP_E_ARG otherwise, as for buffers of different fields); domain_n = 2^a q^b, else PCDHIP_E_SIZE_UNSUPPORTED.  out may be p when
+ * p's buffer is large enough.  The call queues its launches and returns. */
+int pcdhip_fft_general_dev(pcdhip_ctx* ctx, pcdhip_buf* data, size_t n, int inverse, int coset);
+int pcdhip_poly_evals_on_domain(pcdhip_ctx* ctx, const pcdhip_buf* p, size_t len, size_t domain_n, int coset, pcdhip_buf* out);
+
 /* ---- timing helpers (HIP events on the context's stream, for bench.py) ------------------------- */
 int pcdhip_timer_start(pcdhip_ctx* ctx);
 int pcdhip_timer_stop(pcdhip_ctx* ctx, float* out_ms);

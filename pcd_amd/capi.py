@@ -79,6 +79,8 @@ EXPORTS = [
     "pcdhip_msm_short_batch", "pcdhip_msm_short_batch_dev", "pcdhip_kzg_commit_last_plan",
     "pcdhip_domain_bivariate_lagrange", "pcdhip_marlin_mats_upload", "pcdhip_marlin_mats_free", "pcdhip_marlin_mats_info", "pcdhip_marlin_t_evals",
     "pcdhip_marlin_sumcheck_ab", "pcdhip_marlin_sumcheck_f",
+    "pcdhip_marlin_index_build", "pcdhip_marlin_index_free", "pcdhip_marlin_index_info", "pcdhip_marlin_index_timings", "pcdhip_marlin_index_vec", "pcdhip_marlin_index_commit",
+    "pcdhip_fft_general_dev", "pcdhip_poly_evals_on_domain",
 ]
 
 
@@ -113,6 +115,15 @@ def lib():
         _LIB.pcdhip_marlin_t_evals.argtypes = [vp, vp, vp, vp, vp]
         _LIB.pcdhip_marlin_sumcheck_ab.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
         _LIB.pcdhip_marlin_sumcheck_f.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        _LIB.pcdhip_marlin_index_build.argtypes = [vp, C.c_int, vp, vp, vp, sz, sz, sz, sz, sz, C.c_int, vp]
+        _LIB.pcdhip_marlin_index_free.argtypes = [vp, vp]
+        _LIB.pcdhip_marlin_index_free.restype = None
+        _LIB.pcdhip_marlin_index_info.argtypes = [vp, vp]
+        _LIB.pcdhip_marlin_index_timings.argtypes = [vp, vp]
+        _LIB.pcdhip_marlin_index_vec.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+        _LIB.pcdhip_marlin_index_commit.argtypes = [vp, vp, vp, vp, vp]
+        _LIB.pcdhip_fft_general_dev.argtypes = [vp, vp, sz, C.c_int, C.c_int]
+        _LIB.pcdhip_poly_evals_on_domain.argtypes = [vp, vp, sz, sz, C.c_int, vp]
     return _LIB
 
 
@@ -753,6 +764,34 @@ class Context:
                                                                     self._three(col), self._three(row_col), self._three(val), n, out._h))
         return out
 
+    # ---- K10: the index on device
+    def marlin_index_build(self, field, r1cs, domain_h_n, domain_x_n, num_cols=None, domain_k_n=0, domain_b_n=0, keep=0):
+        """the index of `r1cs` (rp_/col_/coeff_{a,b,c}, num_vars): row / col / row_col / val of A, B, C as coefficients, on K and on B
+        (keep: bit 0 / 1 / 2, 0 = all; domain_k_n / domain_b_n 0 = the library's rules) -> MarlinIndex"""
+        A = self._csr(r1cs.rp_a, r1cs.col_a, r1cs.coeff_a)
+        B = self._csr(r1cs.rp_b, r1cs.col_b, r1cs.coeff_b)
+        Cm = self._csr(r1cs.rp_c, r1cs.col_c, r1cs.coeff_c)
+        num_cols = r1cs.num_vars if num_cols is None else int(num_cols)
+        h = C.c_void_p()
+        self._check(lib().pcdhip_marlin_index_build(self._ctx, field, C.byref(A), C.byref(B), C.byref(Cm), num_cols, int(domain_h_n),
+                                                    int(domain_x_n), int(domain_k_n), int(domain_b_n), int(keep), C.byref(h)))
+        return MarlinIndex(self, h, field)
+
+    def fft_general_dev(self, data, n=None, inverse=False, coset=False):
+        """pcdhip_fft_general on the first n (default: all) elements of a DeviceBuf, in place; n = 2^a q^b"""
+        n = data.n if n is None else int(n)
+        self._check(lib().pcdhip_fft_general_dev(self._ctx, data._h, n, int(inverse), int(coset)))
+        return data
+
+    def poly_evals_on_domain(self, p, domain_n, length=None, coset=False, out=None):
+        """the evaluations over the domain of domain_n elements of the polynomial p (`length` coefficients, zero-padded) -> out"""
+        length = p.n if length is None else int(length)
+        domain_n = int(domain_n)
+        own = [] if out is not None else [self.buf_alloc(p.field, domain_n)]
+        out = out if out is not None else own[0]
+        self._call_into(own, lambda: lib().pcdhip_poly_evals_on_domain(self._ctx, p._h, length, domain_n, int(coset), out._h))
+        return out
+
     def kzg_open(self, powers_of_g, p, z_mont, length=None, powers_of_gamma_g=None, blinding=None, blinding_len=None):
         """KZG10::open -> (w Jacobian X||Y||Z, p(z), blinding(z) or None when there is no blinding polynomial)"""
         length = p.n if length is None else int(length)
@@ -935,6 +974,56 @@ class MarlinMats:
     def free(self):
         if self._h:
             lib().pcdhip_marlin_mats_free(self.ctx._ctx, self._h)
+            self._h = None
+
+
+class BorrowedBuf(DeviceBuf):
+    """a DeviceBuf that another handle owns (MarlinIndex.vec): free() leaves the device memory alone"""
+
+    def free(self):
+        self._h = None
+
+
+class MarlinIndex:
+    """pcdhip_marlin_index: form 0 coefficients / 1 evaluations on K / 2 evaluations on B; matrix 0..2 = A, B, C; poly 0..3 = row,
+    col, row_col, val"""
+
+    def __init__(self, ctx, h, field):
+        self.ctx, self._h, self.field = ctx, h, field
+
+    def info(self):
+        """{"domain_k_n", "domain_b_n", "max_nnz", "device_bytes"} (pcdhip_marlin_index_info)"""
+        out = (C.c_uint64 * 4)()
+        self.ctx._check(lib().pcdhip_marlin_index_info(self._h, out))
+        return dict(zip(["domain_k_n", "domain_b_n", "max_nnz", "device_bytes"], [int(v) for v in out]))
+
+    def timings(self):
+        """{"arith_ms", "inverse_ms", "extend_ms"}: device time of the build's parts (pcdhip_marlin_index_timings)"""
+        out = (C.c_float * 3)()
+        self.ctx._check(lib().pcdhip_marlin_index_timings(self._h, out))
+        return dict(zip(["arith_ms", "inverse_ms", "extend_ms"], [float(v) for v in out]))
+
+    def vec(self, form, matrix, poly):
+        """one vector as a borrowed DeviceBuf, valid until the index is freed"""
+        b = C.c_void_p()
+        self.ctx._check(lib().pcdhip_marlin_index_vec(self._h, int(form), int(matrix), int(poly), C.byref(b)))
+        i = self.info()
+        return BorrowedBuf(self.ctx, b, self.field, i["domain_b_n"] if form == 2 else i["domain_k_n"])
+
+    def vecs(self, form):
+        """(row, col, row_col, val), each a list of the three matrices' vectors: the arguments of marlin_sumcheck_ab / _f"""
+        return tuple([self.vec(form, m, q) for m in range(3)] for q in range(4))
+
+    def commit(self, powers):
+        """the twelve index commitments, matrix-major -> (comm_xy (12, L), comm_inf (12,))"""
+        comm = np.zeros((12, point_limbs(powers.curve, G1)), dtype=np.uint64)
+        cinf = np.zeros(12, dtype=np.uint8)
+        self.ctx._check(lib().pcdhip_marlin_index_commit(self.ctx._ctx, self._h, powers._h, _p(comm), _p(cinf)))
+        return comm, cinf
+
+    def free(self):
+        if self._h:
+            lib().pcdhip_marlin_index_free(self.ctx._ctx, self._h)
             self._h = None
 
 

@@ -6,6 +6,9 @@ using namespace pcd;
 namespace {
 const uint32_t kSmallSubgroupBase[4] = {7, 0, 5, 0};  // ark-ff SMALL_SUBGROUP_BASE (adicity 2) of the two help fields
 
+}  // namespace
+
+namespace pcd {
 int split_domain(int field_id, size_t n, Dom* d) {  // n = m * 2^a with m in {1, q, q^2}?
   if (n == 0 || n >= (1ull << 31)) return PCDHIP_E_ARG;
   const uint32_t q = kSmallSubgroupBase[field_id];
@@ -19,9 +22,6 @@ int split_domain(int field_id, size_t n, Dom* d) {  // n = m * 2^a with m in {1,
   d->n = (uint32_t)n; d->m = m; d->a = a;
   return PCDHIP_OK;
 }
-}  // namespace
-
-namespace pcd {
 int pick_domain(int field_id, size_t min_size, Dom* d) {
   const FieldEntry& fe = field_entry(field_id);
   int log_n = 0;
@@ -126,6 +126,35 @@ int pcdhip_fft(pcdhip_ctx* ctx, int field_id, uint64_t* data, uint32_t log_n, in
   BIND();
   Dom d = {1u << log_n, 1, (int)log_n};
   return fft_host_general(ctx, field_id, data, d, inverse, coset);
+}
+int pcdhip_fft_general_dev(pcdhip_ctx* ctx, pcdhip_buf* data, size_t n, int inverse, int coset) {
+  if (!ctx || !data) return PCDHIP_E_ARG;
+  Dom d;
+  int rc = split_domain(data->field_id, n, &d);
+  if (rc) return rc;
+  BIND();
+  return fft_dev_general(ctx, data, d, inverse, coset);
+}
+// p (len coefficients, ABI words) -> its device image in AUX_FFT_X with a zero tail up to the domain, the forward transform, -> out
+int pcdhip_poly_evals_on_domain(pcdhip_ctx* ctx, const pcdhip_buf* p, size_t len, size_t domain_n, int coset, pcdhip_buf* out) {
+  if (!ctx || !p || !out || p->field_id != out->field_id || len > p->n) return PCDHIP_E_ARG;
+  Dom d;
+  int rc = split_domain(p->field_id, domain_n, &d);
+  if (rc) return rc == PCDHIP_E_ARG ? PCDHIP_E_SIZE_UNSUPPORTED : rc;
+  if (len > domain_n || domain_n > out->n) return PCDHIP_E_ARG;
+  BIND();
+  const FieldEntry& fe = field_entry(p->field_id);
+  const size_t vb = (size_t)d.n * fe.words * 4;
+  TRY(ctx->aux_ws.ensure(AUX_FFT_X, vb));
+  TRY(ctx->aux_ws.ensure(AUX_FFT_TMP, vb));
+  uint32_t* x = (uint32_t*)ctx->aux_ws.buf[AUX_FFT_X];
+  TRY(fe.convert(ctx->stream, p->dptr, x, (uint32_t)len, 0));
+  if (len < d.n) TRY(hipMemsetAsync(x + len * fe.words, 0, (d.n - len) * fe.words * 4, ctx->stream));  // (the device image of 0 is all zero words)
+  // (the domain of one element: its only point is 1, or the coset's g, and the polynomial is the constant p_0)
+  if (d.n > 1) rc = domain_transform(ctx, p->field_id, d, x, (uint32_t*)ctx->aux_ws.buf[AUX_FFT_TMP], 0, coset ? 1 : 0, nullptr, nullptr);
+  if (rc) return rc;
+  TRY(fe.convert(ctx->stream, x, out->dptr, d.n, 1));
+  return PCDHIP_OK;
 }
 int pcdhip_fft_general(pcdhip_ctx* ctx, int field_id, uint64_t* data, size_t n, int inverse, int coset) {
   if (!ctx || !data || !valid_field(field_id)) return PCDHIP_E_ARG;

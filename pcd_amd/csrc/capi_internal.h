@@ -88,6 +88,7 @@ int msm_short_batch_async(pcdhip_ctx* ctx, const pcdhip_bases* bases, const MsmS
 
 // ---- capi_fft.hip
 int pick_domain(int field_id, size_t min_size, Dom* d);
+int split_domain(int field_id, size_t n, Dom* d);  // n = m * 2^a with m in {1, q, q^2}?  PCDHIP_E_ARG for 0 and n >= 2^31, else E_SIZE_UNSUPPORTED
 int get_tables(pcdhip_ctx* ctx, int field_id, int log_n, const FftTables** out);
 int get_mixed_tables(pcdhip_ctx* ctx, int field_id, const Dom& d, const FftTables** out);
 int domain_transform(pcdhip_ctx* ctx, int field_id, const Dom& d, uint32_t* v, uint32_t* tmp, int inverse, int coset, float* pass_ms,

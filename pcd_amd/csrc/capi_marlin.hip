@@ -1,6 +1,8 @@
 // ------------------------------------------------------------------------------------------------ K9: Marlin's AHP rounds 2 and 3
 // (marlin.hip.h and the t(X) kernels of inst_field.hip: r(alpha, .) on H, the transposed mat-vec behind t(X), the rational sumcheck).
 // Every call queues its launches on the context's stream and returns: nothing here waits for the device except the upload of the matrices.
+// K10, the index on device (the arithmetisation onto K, the coefficients, the evaluations on B, the twelve commitments), follows below;
+// pcdhip_marlin_index_build waits for its own uploads and for the end of its work.
 #include <stdlib.h>
 
 #include "capi_internal.h"
@@ -198,6 +200,226 @@ int pcdhip_marlin_sumcheck_f(pcdhip_ctx* ctx, const uint64_t* alpha_mont, const 
   TRY(fe.vec_batch_inverse(ctx->stream, bv, n, nullptr, bv));
   TRY(fe.vec_mul(ctx->stream, av, bv, n, f_out->dptr, 1));
   return PCDHIP_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ K10: the index on device
+// One matrix in the index's entry order: row by row, ascending column inside a row, equal columns as the CSR gives them.  A matrix whose
+// rows are ascending already is uploaded from the caller's arrays as they stand; otherwise col and coeff are copied and the offending
+// rows sorted stably (an index permutation per row).
+namespace {
+struct OrderedCsr {
+  const uint32_t* col; const uint64_t* coeff;
+  std::vector<uint32_t> col_own; std::vector<uint64_t> coeff_own;
+};
+void order_csr(const pcdhip_csr* m, size_t limbs, OrderedCsr* o) {
+  o->col = m->col; o->coeff = m->coeff;
+  std::vector<uint32_t> perm;
+  for (uint64_t r = 0; r < m->num_rows; r++) {
+    const uint64_t lo = m->row_ptr[r], hi = m->row_ptr[r + 1];
+    bool ascending = true;
+    for (uint64_t k = lo + 1; k < hi && ascending; k++) ascending = m->col[k - 1] <= m->col[k];
+    if (ascending) continue;
+    if (o->col_own.empty()) {
+      const uint64_t nnz = m->row_ptr[m->num_rows];
+      o->col_own.assign(m->col, m->col + nnz);
+      o->coeff_own.assign(m->coeff, m->coeff + nnz * limbs);
+      o->col = o->col_own.data(); o->coeff = o->coeff_own.data();
+    }
+    perm.resize(hi - lo);
+    for (uint64_t k = lo; k < hi; k++) perm[k - lo] = (uint32_t)(k - lo);
+    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return m->col[lo + a] < m->col[lo + b]; });
+    for (uint64_t k = lo; k < hi; k++) {
+      o->col_own[k] = m->col[lo + perm[k - lo]];
+      memcpy(&o->coeff_own[k * limbs], m->coeff + (lo + perm[k - lo]) * limbs, limbs * 8);
+    }
+  }
+}
+void index_release(pcdhip_marlin_index* h) {
+  for (int f = 0; f < 3; f++) if (h->block[f]) (void)hipFree(h->block[f]);
+  delete h;
+}
+inline size_t up64(size_t x) { return (x + 63) & ~(size_t)63; }
+// the events behind pcdhip_marlin_index_timings: [0], [1] around the arithmetisation, then per vector its start, its coefficients, its
+// evaluations on B.  Recording one does not wait for the device; the times are read after the build's own final wait
+struct BuildEvents {
+  hipEvent_t ev[2 + 3 * 12] = {};
+  hipError_t make() {
+    for (hipEvent_t& e : ev) { hipError_t rc = hipEventCreate(&e); if (rc != hipSuccess) return rc; }
+    return hipSuccess;
+  }
+  ~BuildEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+}  // namespace
+
+extern "C" {
+
+int pcdhip_marlin_index_build(pcdhip_ctx* ctx, int field_id, const pcdhip_csr* A, const pcdhip_csr* B, const pcdhip_csr* C, size_t num_cols,
+                              size_t domain_h_n, size_t domain_x_n, size_t domain_k_n, size_t domain_b_n, int keep, pcdhip_marlin_index** out) {
+  if (!ctx || !valid_field(field_id) || !A || !B || !C || !out || keep < 0 || keep > 7) return PCDHIP_E_ARG;
+  if (!is_domain_size(field_id, domain_h_n) || !is_domain_size(field_id, domain_x_n) || domain_h_n % domain_x_n != 0) return PCDHIP_E_ARG;
+  if (A->num_rows != B->num_rows || A->num_rows != C->num_rows || A->num_rows > domain_h_n || num_cols > domain_h_n) return PCDHIP_E_ARG;
+  const pcdhip_csr* ms[3] = {A, B, C};
+  size_t max_nnz = 0;
+  for (int k = 0; k < 3; k++) {
+    int rc = validate_csr(ms[k], num_cols);
+    if (rc) return rc;
+    max_nnz = std::max<size_t>(max_nnz, ms[k]->row_ptr[ms[k]->num_rows]);
+  }
+  if (keep == 0) keep = 7;
+  // the two domains: the rules of the header, or the caller's sizes
+  Dom dk, db, dh;
+  if (domain_k_n) {
+    if (split_domain(field_id, domain_k_n, &dk) != PCDHIP_OK || domain_k_n < max_nnz) return PCDHIP_E_ARG;
+  } else if (pick_domain(field_id, std::max<size_t>(max_nnz, 1), &dk) != PCDHIP_OK) return PCDHIP_E_SIZE_UNSUPPORTED;
+  if (domain_b_n) {
+    if (split_domain(field_id, domain_b_n, &db) != PCDHIP_OK || domain_b_n < dk.n) return PCDHIP_E_ARG;
+  } else if (3 * (size_t)dk.n >= kMaxLen || pick_domain(field_id, std::max<size_t>(3 * (size_t)dk.n - 3, 1), &db) != PCDHIP_OK) return PCDHIP_E_SIZE_UNSUPPORTED;
+  if (pick_domain(field_id, domain_h_n, &dh) != PCDHIP_OK) return PCDHIP_E_ARG;
+  BIND();
+  return guarded([&]() -> int {
+    const FieldEntry& fe = field_entry(field_id);
+    const size_t limbs = (size_t)fe.abi_words / 2, eb = (size_t)fe.abi_words * 4, rows = A->num_rows;
+    const bool want_b = (keep & 4) != 0;
+    // the resident powers of H's generator (none for |H| = 1)
+    const FftTables* th = nullptr;
+    if (dh.n > 1) {
+      int rc = dh.m == 1 ? get_tables(ctx, field_id, dh.a, &th) : get_mixed_tables(ctx, field_id, dh, &th);
+      if (rc) return rc;
+    }
+    pcdhip_marlin_index* h = new pcdhip_marlin_index();
+    h->field_id = field_id; h->domain_h_n = domain_h_n; h->domain_x_n = domain_x_n; h->domain_k_n = dk.n; h->domain_b_n = db.n;
+    h->max_nnz = max_nnz;
+    void* csr_dev = nullptr;
+    auto bail = [&](int rc) { if (csr_dev) (void)hipFree(csr_dev); index_release(h); return rc; };
+    // the evaluations on K are always made; coefficients and evaluations on B only where they are kept
+    const size_t form_n[3] = {dk.n, dk.n, db.n};
+    const bool form_on[3] = {(keep & 1) != 0, true, want_b};
+    for (int f = 0; f < 3; f++) {
+      if (!form_on[f]) continue;
+      hipError_t e = hipMalloc(&h->block[f], 12 * form_n[f] * eb);
+      if (e != hipSuccess) return bail(fail(ctx, e));
+      for (int m = 0; m < 3; m++) for (int q = 0; q < 4; q++) {
+        h->vec[f][m][q].field_id = field_id; h->vec[f][m][q].n = form_n[f];
+        h->vec[f][m][q].dptr = (uint32_t*)((char*)h->block[f] + (size_t)(4 * m + q) * form_n[f] * eb);
+      }
+    }
+    // the three CSRs in the index's order, one device block: per matrix rp, coeff, col
+    OrderedCsr oc[3];
+    size_t base[3], total = 0;
+    for (int k = 0; k < 3; k++) {
+      order_csr(ms[k], limbs, &oc[k]);
+      const size_t nnz = ms[k]->row_ptr[rows];
+      base[k] = total;
+      total += up64((rows + 1) * 8) + up64(nnz * eb) + up64(nnz * 4);
+    }
+    hipError_t e = hipMalloc(&csr_dev, total + 64);
+    if (e != hipSuccess) return bail(fail(ctx, e));
+    MarlinIndexIn in;
+    for (int k = 0; k < 3 && e == hipSuccess; k++) {
+      const size_t nnz = ms[k]->row_ptr[rows];
+      char* d = (char*)csr_dev + base[k];
+      char* dco = d + up64((rows + 1) * 8);
+      char* dcol = dco + up64(nnz * eb);
+      e = hipMemcpyAsync(d, ms[k]->row_ptr, (rows + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+      if (e == hipSuccess && nnz) e = hipMemcpyAsync(dco, oc[k].coeff, nnz * eb, hipMemcpyHostToDevice, ctx->stream);
+      if (e == hipSuccess && nnz) e = hipMemcpyAsync(dcol, oc[k].col, nnz * 4, hipMemcpyHostToDevice, ctx->stream);
+      in.rp[k] = (const uint64_t*)d; in.coeff[k] = (const uint32_t*)dco; in.col[k] = (const uint32_t*)dcol; in.nnz[k] = (uint32_t)nnz;
+      for (int q = 0; q < 4; q++) in.out[k][q] = h->vec[1][k][q].dptr;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the caller's arrays and the sorted copies are done with
+    if (e != hipSuccess) return bail(fail(ctx, e));
+    in.rows = (uint32_t)rows; in.k_n = dk.n; in.x_n = (uint32_t)domain_x_n; in.period = (uint32_t)(domain_h_n / domain_x_n);
+    BuildEvents be;
+    e = be.make();
+    if (e == hipSuccess) e = hipEventRecord(be.ev[0], ctx->stream);
+    if (e == hipSuccess) e = fe.marlin_index_arith(ctx->stream, th ? th->consts : nullptr, th ? th->tw_fwd : nullptr, dh.n / dh.m, in);
+    if (e == hipSuccess) e = hipEventRecord(be.ev[1], ctx->stream);
+    if (e != hipSuccess) return bail(fail(ctx, e));
+    const bool transforms = (keep & 1) || want_b;
+    // per vector: evaluations on K -> device image -> inverse transform on K (the coefficients) -> zero tail up to |B| -> forward
+    // transform on B; the ABI images of the kept forms are written on the way
+    if (transforms) {
+      const size_t big = want_b ? db.n : dk.n, vb = big * fe.words * 4;
+      e = ctx->aux_ws.ensure(AUX_FFT_X, vb);
+      if (e == hipSuccess) e = ctx->aux_ws.ensure(AUX_FFT_TMP, vb);
+      if (e != hipSuccess) return bail(fail(ctx, e));
+      uint32_t *x = (uint32_t*)ctx->aux_ws.buf[AUX_FFT_X], *tmp = (uint32_t*)ctx->aux_ws.buf[AUX_FFT_TMP];
+      for (int m = 0; m < 3; m++) for (int q = 0; q < 4; q++) {
+        hipEvent_t* const ev = be.ev + 2 + 3 * (4 * m + q);
+        e = hipEventRecord(ev[0], ctx->stream);
+        if (e == hipSuccess) e = fe.convert(ctx->stream, h->vec[1][m][q].dptr, x, dk.n, 0);
+        if (e != hipSuccess) return bail(fail(ctx, e));
+        int rc = dk.n > 1 ? domain_transform(ctx, field_id, dk, x, tmp, 1, 0, nullptr, nullptr) : PCDHIP_OK;  // (|K| = 1: a constant)
+        if (rc) return bail(rc);
+        if (keep & 1) e = fe.convert(ctx->stream, x, h->vec[0][m][q].dptr, dk.n, 1);
+        if (e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
+        if (e != hipSuccess) return bail(fail(ctx, e));
+        if (!want_b) continue;
+        if (db.n > dk.n) e = hipMemsetAsync(x + (size_t)dk.n * fe.words, 0, (size_t)(db.n - dk.n) * fe.words * 4, ctx->stream);
+        if (e != hipSuccess) return bail(fail(ctx, e));
+        rc = db.n > 1 ? domain_transform(ctx, field_id, db, x, tmp, 0, 0, nullptr, nullptr) : PCDHIP_OK;
+        if (rc) return bail(rc);
+        e = fe.convert(ctx->stream, x, h->vec[2][m][q].dptr, db.n, 1);
+        if (e == hipSuccess) e = hipEventRecord(ev[2], ctx->stream);
+        if (e != hipSuccess) return bail(fail(ctx, e));
+      }
+    }
+    // the CSRs, and the evaluations on K when they were not asked for, go once the device is done with them
+    e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return bail(fail(ctx, e));
+    (void)hipEventElapsedTime(&h->ms[0], be.ev[0], be.ev[1]);
+    for (int i = 0; i < 12 && transforms; i++) {
+      float t = 0;
+      if (hipEventElapsedTime(&t, be.ev[2 + 3 * i], be.ev[3 + 3 * i]) == hipSuccess) h->ms[1] += t;
+      if (want_b && hipEventElapsedTime(&t, be.ev[3 + 3 * i], be.ev[4 + 3 * i]) == hipSuccess) h->ms[2] += t;
+    }
+    (void)hipFree(csr_dev);
+    if (!(keep & 2)) { (void)hipFree(h->block[1]); h->block[1] = nullptr; }
+    *out = h;
+    return PCDHIP_OK;
+  });
+}
+
+void pcdhip_marlin_index_free(pcdhip_ctx* ctx, pcdhip_marlin_index* index) {
+  if (!index) return;
+  if (ctx) (void)hipSetDevice(ctx->device);
+  index_release(index);
+}
+
+int pcdhip_marlin_index_info(const pcdhip_marlin_index* index, uint64_t out[4]) {
+  if (!index || !out) return PCDHIP_E_ARG;
+  const size_t eb = (size_t)field_entry(index->field_id).abi_words * 4;
+  out[0] = index->domain_k_n; out[1] = index->domain_b_n; out[2] = index->max_nnz;
+  out[3] = 0;
+  for (int f = 0; f < 3; f++) if (index->block[f]) out[3] += 12 * (f == 2 ? index->domain_b_n : index->domain_k_n) * eb;
+  return PCDHIP_OK;
+}
+
+int pcdhip_marlin_index_timings(const pcdhip_marlin_index* index, float out_ms[3]) {
+  if (!index || !out_ms) return PCDHIP_E_ARG;
+  memcpy(out_ms, index->ms, sizeof index->ms);
+  return PCDHIP_OK;
+}
+
+int pcdhip_marlin_index_vec(const pcdhip_marlin_index* index, int form, int matrix, int poly, const pcdhip_buf** out) {
+  if (!index || !out || form < 0 || form > 2 || matrix < 0 || matrix > 2 || poly < 0 || poly > 3) return PCDHIP_E_ARG;
+  if (!index->block[form]) return PCDHIP_E_ARG;
+  *out = &index->vec[form][matrix][poly];
+  return PCDHIP_OK;
+}
+
+int pcdhip_marlin_index_commit(pcdhip_ctx* ctx, const pcdhip_marlin_index* index, const pcdhip_bases* powers_of_g, uint64_t* comm_xy,
+                               uint8_t* comm_inf) {
+  if (!ctx || !index || !powers_of_g || !comm_xy || !comm_inf || !index->block[0]) return PCDHIP_E_ARG;
+  pcdhip_kzg_commit_item items[12];
+  memset(items, 0, sizeof items);
+  for (int m = 0; m < 3; m++) for (int q = 0; q < 4; q++) {
+    items[4 * m + q].poly = &index->vec[0][m][q];
+    items[4 * m + q].len = index->domain_k_n;
+  }
+  return pcdhip_kzg_commit(ctx, powers_of_g, nullptr, nullptr, items, 12, comm_xy, comm_inf, nullptr, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -71,6 +71,26 @@ struct MarlinMatsDev {
   const uint32_t* long_out = nullptr; const uint32_t* long_seg_lo = nullptr; uint32_t n_long_out = 0;
 };
 }
+namespace pcd {
+// K10 (pcdhip_marlin_index_build): what one launch of the arithmetisation reads and writes.  The three matrices as plain CSRs in the
+// index's entry order (row by row, ascending column inside a row; coefficients as ABI words), and per matrix the four vectors on K
+// (row, col, row_col, val; k_n elements each, ABI words)
+struct MarlinIndexIn {
+  const uint64_t* rp[3]; const uint32_t* col[3]; const uint32_t* coeff[3];
+  uint32_t* out[3][4];
+  uint32_t nnz[3];
+  uint32_t rows, k_n, x_n, period;  // period = |H| / |X|
+};
+}
+// the index of one constraint system (capi_marlin.hip): per form (coefficients on K, evaluations on K, evaluations on B) one device block
+// of twelve vectors, matrix-major, and the borrowed handles into it
+struct pcdhip_marlin_index {
+  int field_id = 0;
+  size_t domain_h_n = 0, domain_x_n = 0, domain_k_n = 0, domain_b_n = 0, max_nnz = 0;
+  void* block[3] = {nullptr, nullptr, nullptr};  // null: the form was not kept
+  pcdhip_buf vec[3][3][4];                       // [form][matrix][poly]
+  float ms[3] = {0, 0, 0};                       // device time of the build: the arithmetisation, the 12 inverse transforms, the 12 extensions
+};
 struct pcdhip_marlin_mats {
   int field_id = 0;
   size_t domain_h_n = 0, domain_x_n = 0, num_rows = 0, num_cols = 0;
@@ -302,6 +322,9 @@ struct FieldEntry {
   hipError_t (*marlin_sumcheck_ab)(hipStream_t, const uint32_t* alpha_abi, const uint32_t* beta_abi, const uint32_t* coeff_abi,
                                    const uint32_t* const row[3], const uint32_t* const col[3], const uint32_t* const rc[3],
                                    const uint32_t* const val[3], uint64_t n, uint32_t* a_out, uint32_t* b_out);
+  // K10 (marlin.hip.h marlin_index_arith): the twelve evaluation vectors on K of an index, one launch.  domain_consts / tw / tw_len of
+  // the domain H as for marlin_lagrange (null, null, 1 for |H| = 1)
+  hipError_t (*marlin_index_arith)(hipStream_t, const void* domain_consts, const uint32_t* tw, uint32_t tw_len, const MarlinIndexIn& in);
 };
 const FieldEntry& field_entry(int field_id);
 

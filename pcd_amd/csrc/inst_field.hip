@@ -35,12 +35,15 @@ static_assert(sizeof(FTP) == sizeof(FT), "same image");
 
 #define PCD_CAT_(a, b) a##b
 #define PCD_CAT(a, b) PCD_CAT_(a, b)
-// inst_marlin.hip, the same field: the differences x - w^i (and the scale x^n - 1 in ABI words into vh_abi), the sumcheck's a and b
+// inst_marlin.hip, the same field: the differences x - w^i (and the scale x^n - 1 in ABI words into vh_abi), the sumcheck's a and b,
+// the index's arithmetisation
 hipError_t PCD_CAT(pcd_marlin_diffs_, PCD_FIELD_IDX)(hipStream_t, const void* domain_consts, const uint32_t* tw, uint32_t tw_len,
                                                      const uint32_t* x_abi, uint64_t n, uint32_t* out, uint32_t* vh_abi);
 hipError_t PCD_CAT(pcd_marlin_sumcheck_ab_, PCD_FIELD_IDX)(hipStream_t, const uint32_t* alpha_abi, const uint32_t* beta_abi, const uint32_t* coeff_abi,
                                                            const uint32_t* const row[3], const uint32_t* const col[3], const uint32_t* const rc[3],
                                                            const uint32_t* const val[3], uint64_t n, uint32_t* a_out, uint32_t* b_out);
+hipError_t PCD_CAT(pcd_marlin_index_arith_, PCD_FIELD_IDX)(hipStream_t, const void* domain_consts, const uint32_t* tw, uint32_t tw_len,
+                                                           const MarlinIndexIn& in);
 
 namespace {
 
@@ -639,7 +642,7 @@ const FieldEntry* PCD_CAT(pcd_field_entry_, PCD_FIELD_IDX)() {
                                mixed_make_tables, mixed_run, mixed_mul_sub_divz, scale_canon, SETUP_CONSTS, setup_scalars, run_batched_entry, spmv3,
                                poly_scratch_words, poly_eval, poly_lincomb_run, vec_mul_run, vec_batch_inverse_run,
                                poly_div_vanishing_run, poly_commit_scalars_run, marlin_lagrange_run, marlin_t_evals_run,
-                               PCD_CAT(pcd_marlin_sumcheck_ab_, PCD_FIELD_IDX)};
+                               PCD_CAT(pcd_marlin_sumcheck_ab_, PCD_FIELD_IDX), PCD_CAT(pcd_marlin_index_arith_, PCD_FIELD_IDX)};
   return &e;
 }
 

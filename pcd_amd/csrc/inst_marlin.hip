@@ -1,5 +1,5 @@
 // One object per scalar field (compile with -DPCD_FIELD_IDX=0..3): the K9 kernels whose products are inlined (marlin.hip.h) -- the
-// differences behind r(alpha, .) on H and the rational sumcheck.  A unit of its own so that their 753-bit bodies compile beside the
+// differences behind r(alpha, .) on H, the rational sumcheck, and the K10 arithmetisation of the index.  A unit of its own so that their 753-bit bodies compile beside the
 // field objects; inst_field.hip puts the two entries into its FieldEntry.
 #include "common.h"
 #include <string.h>
@@ -47,6 +47,30 @@ hipError_t PCD_CAT(pcd_marlin_sumcheck_ab_, PCD_FIELD_IDX)(hipStream_t st, const
   MarlinSumcheckIn in;
   for (int m = 0; m < 3; m++) { in.row[m] = row[m]; in.col[m] = col[m]; in.rc[m] = rc[0] ? rc[m] : nullptr; in.val[m] = val[m]; }
   hipLaunchKernelGGL(marlin_sumcheck_ab<FTP>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, k, in, n, a_out, b_out);
+  return hipGetLastError();
+}
+
+// K10: the twelve evaluation vectors on K of an index.  1 / |H| comes from the domain's constants (slot 4 of DomainConsts and of
+// MixedConsts, device image); |H| = 1 has no tables and w = 1 / |H| = 1
+hipError_t PCD_CAT(pcd_marlin_index_arith_, PCD_FIELD_IDX)(hipStream_t st, const void* domain_consts, const uint32_t* tw, uint32_t tw_len,
+                                                           const MarlinIndexIn& in) {
+  if (in.k_n == 0) return hipSuccess;
+  MarlinIndexArgs<FTP> a;
+  for (int m = 0; m < 3; m++) {
+    a.rp[m] = in.rp[m]; a.col[m] = in.col[m]; a.coeff[m] = in.coeff[m]; a.nnz[m] = in.nnz[m];
+    for (int q = 0; q < 4; q++) a.out[m][q] = in.out[m][q];
+  }
+  a.rows = in.rows; a.k_n = in.k_n; a.x_n = in.x_n; a.period = in.period;
+  a.tw = tw; a.tw_len = tw ? tw_len : 1;
+  FTP w = FTP::one();
+  a.h_inv = FTP::one();
+  if (domain_consts) {
+    memcpy(&w, domain_consts, sizeof w);
+    memcpy(&a.h_inv, (const char*)domain_consts + 4 * sizeof(FTP), sizeof a.h_inv);
+  }
+  a.w_len = tw ? w.pow_u64(tw_len) : FTP::one();
+  FTP::one().to_abi(a.one_abi.w);
+  hipLaunchKernelGGL(marlin_index_arith<FTP>, dim3((in.k_n + 255) / 256, 3), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

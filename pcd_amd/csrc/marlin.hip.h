@@ -114,4 +114,83 @@ __global__ void __launch_bounds__(256) marlin_sumcheck_ab(const MarlinSumcheckCo
   if (i < n) marlin_sumcheck_element<F>(k, in, i, a_out, b_out);
 }
 
+// ---- K10, the index's arithmetisation: the row / col / row_col / val evaluations on K of the three constraint matrices, one launch.
+// Lane k of matrix M (blockIdx.y) owns entry k of M in the index's order -- row by row, ascending column inside a row, which is how the
+// host lays the CSR out before the upload -- and writes, as ABI words,
+//   row_k = w^pi(c)   col_k = w^r   row_col_k = row_k col_k   val_k = v w^pi(c) / |H|          for k < nnz_M,
+//   row_k = col_k = row_col_k = 1,  val_k = 0                                                   for nnz_M <= k < |K|.
+// r: the row that holds entry k, found in the resident row pointers -- the largest r with rp[r] <= k, which steps over runs of empty
+// rows (their pointers are equal, and the search keeps the last of them that is not beyond k).  pi = reindex_by_subdomain in the
+// lane; with period == 1 (|X| = |H|) every column is an instance column, so the quotient by period - 1 is never formed.  w^j from the
+// transform's resident powers, as in marlin_lagrange_diffs: beyond the table of a mixed-radix H, times (w^tw_len)^(j / tw_len).
+// Scales: the table holds w^j R'; times cout = R it is w^j R, the ABI image (row, col).  row_col = (w^pi(c) R') (w^r R) / R'.
+// val = (v R as read) (w^pi(c) / |H| R') / R', the second factor one product with the host's constant h_inv = R' / |H|.
+// Product sites: the power beyond the table (pow_u64's two and one more; never taken by a radix-2 H), one for the three products with
+// a constant (a loop: cout, cout, h_inv), row_col and val.
+template <class F>
+struct MarlinIndexArgs {
+  const uint64_t* rp[3];     // rows + 1 entries each
+  const uint32_t* col[3];    // nnz_M column indices, the index's order
+  const uint32_t* coeff[3];  // nnz_M coefficients, ABI words
+  uint32_t* out[3][4];       // row, col, row_col, val: k_n elements each, ABI words
+  uint32_t nnz[3];
+  uint32_t rows, k_n;
+  uint32_t x_n, period;      // |X| and |H| / |X|
+  const uint32_t* tw;        // tw_len resident powers of w (device image); null for |H| = 1
+  uint32_t tw_len;
+  F w_len;                   // w^tw_len
+  F h_inv;                   // 1 / |H| on the scale R'
+  PolyAbiElt<F> one_abi;     // the ABI words of 1
+};
+
+template <class F>
+PCD_DEV F marlin_domain_power(const uint32_t* __restrict__ tw, uint32_t tw_len, const F& w_len, uint32_t j) {
+  if (!tw) return F::one();
+  F p = F::load(tw + (size_t)(j % tw_len) * F::WORDS);
+  if (j >= tw_len) p = p * w_len.pow_u64(j / tw_len);
+  return p;
+}
+
+template <class F>
+__global__ void __launch_bounds__(256) marlin_index_arith(const MarlinIndexArgs<F> a) {
+  constexpr int AW = F::ABI_WORDS;
+  const uint32_t M = blockIdx.y;
+  const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= a.k_n) return;
+  uint32_t* const row_out = a.out[M][0] + (size_t)k * AW;
+  uint32_t* const col_out = a.out[M][1] + (size_t)k * AW;
+  uint32_t* const rc_out = a.out[M][2] + (size_t)k * AW;
+  uint32_t* const val_out = a.out[M][3] + (size_t)k * AW;
+  if (k >= a.nnz[M]) {
+#pragma unroll
+    for (int i = 0; i < AW; i++) { row_out[i] = a.one_abi.w[i]; col_out[i] = a.one_abi.w[i]; rc_out[i] = a.one_abi.w[i]; val_out[i] = 0; }
+    return;
+  }
+  // the row of entry k: rp[lo] <= k < rp[hi] throughout (rp[0] = 0, rp[rows] = nnz > k)
+  const uint64_t* __restrict__ rp = a.rp[M];
+  uint32_t lo = 0, hi = a.rows;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (rp[mid] <= k) lo = mid; else hi = mid;
+  }
+  const uint32_t c = a.col[M][k];
+  uint32_t j;
+  if (a.period == 1 || c < a.x_n) j = c * a.period;
+  else { const uint32_t i = c - a.x_n; j = i + i / (a.period - 1) + 1; }
+  F cout;
+#pragma unroll
+  for (int i = 0; i < F::N; i++) cout.v[i] = F::Params::cout(i);
+  F wj = F::zero(), wh = F::zero(), col_r = F::zero();
+#pragma unroll 1
+  for (int s = 0; s < 3; s++) {  // s = 0: col = w^r R;  1: row = w^j R;  2: wh = w^j / |H| on the scale R'
+    const F p = s == 2 ? wj : marlin_domain_power<F>(a.tw, a.tw_len, a.w_len, s == 0 ? lo : j);
+    const F o = p * (s == 2 ? a.h_inv : cout);
+    if (s == 0) { col_r = o; o.canonical().pack32(col_out); }
+    else if (s == 1) { wj = p; o.canonical().pack32(row_out); }
+    else wh = o;
+  }
+  (wj * col_r).canonical().pack32(rc_out);
+  (F::unpack32(a.coeff[M] + (size_t)k * AW) * wh).canonical().pack32(val_out);
+}
+
 }  // namespace pcd

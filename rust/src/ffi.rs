@@ -8,6 +8,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct pcdhip_buf { _p: [u8; 0] }
 #[repr(C)] pub struct pcdhip_g16_pk { _p: [u8; 0] }
 #[repr(C)] pub struct pcdhip_pvk { _p: [u8; 0] }
+#[repr(C)] pub struct pcdhip_marlin_index { _p: [u8; 0] }
 #[repr(C)] pub struct pcdhip_csr { pub num_rows: u64, pub row_ptr: *const u64, pub col: *const u32, pub coeff: *const u64 }
 #[repr(C)]
 pub struct pcdhip_g16_pk_host {
@@ -98,6 +99,20 @@ extern "C" {
                              shifted_powers_of_g: *const pcdhip_bases, items: *const pcdhip_kzg_commit_item, k: usize, comm_xy: *mut u64,
                              comm_inf: *mut u8, shifted_xy: *mut u64, shifted_inf: *mut u8, trimmed_len: *mut u64) -> c_int;
     pub fn pcdhip_kzg_commit_last_plan(ctx: *mut pcdhip_ctx, out: *mut u64) -> c_int;
+    // K10: the Marlin index on device (row / col / row_col / val of A, B, C on K and B, the twelve commitments) and the two device
+    // transforms it is made of
+    pub fn pcdhip_marlin_index_build(ctx: *mut pcdhip_ctx, field: c_int, a: *const pcdhip_csr, b: *const pcdhip_csr, c: *const pcdhip_csr,
+                                     num_cols: usize, domain_h_n: usize, domain_x_n: usize, domain_k_n: usize, domain_b_n: usize, keep: c_int,
+                                     out: *mut *mut pcdhip_marlin_index) -> c_int;
+    pub fn pcdhip_marlin_index_free(ctx: *mut pcdhip_ctx, index: *mut pcdhip_marlin_index);
+    pub fn pcdhip_marlin_index_info(index: *const pcdhip_marlin_index, out: *mut u64) -> c_int;
+    pub fn pcdhip_marlin_index_timings(index: *const pcdhip_marlin_index, out_ms: *mut f32) -> c_int;
+    pub fn pcdhip_marlin_index_vec(index: *const pcdhip_marlin_index, form: c_int, matrix: c_int, poly: c_int, out: *mut *const pcdhip_buf) -> c_int;
+    pub fn pcdhip_marlin_index_commit(ctx: *mut pcdhip_ctx, index: *const pcdhip_marlin_index, powers_of_g: *const pcdhip_bases, comm_xy: *mut u64,
+                                      comm_inf: *mut u8) -> c_int;
+    pub fn pcdhip_fft_general_dev(ctx: *mut pcdhip_ctx, data: *mut pcdhip_buf, n: usize, inverse: c_int, coset: c_int) -> c_int;
+    pub fn pcdhip_poly_evals_on_domain(ctx: *mut pcdhip_ctx, p: *const pcdhip_buf, len: usize, domain_n: usize, coset: c_int,
+                                       out: *mut pcdhip_buf) -> c_int;
 }
 
 /// `PCDHIP_E_*` (include/pcdhip.h)
