@@ -669,6 +669,87 @@ int pcdhip_marlin_index_commit(pcdhip_ctx* ctx, const pcdhip_marlin_index* index
 int pcdhip_fft_general_dev(pcdhip_ctx* ctx, pcdhip_buf* data, size_t n, int inverse, int coset);
 int pcdhip_poly_evals_on_domain(pcdhip_ctx* ctx, const pcdhip_buf* p, size_t len, size_t domain_n, int coset, pcdhip_buf* out);
 
+/* ---- K11 Marlin's round 1 and the first sumcheck: w, z_A, z_B, h_1, g_1 ----------------------------------------------------------
+ * The first half of ark-marlin's prover, on the conventions of K9 / K10: device vectors of ABI Montgomery elements of ONE scalar field,
+ * the context's own stream and workspaces, device 0 of a multi-device context, host field elements as ABI Montgomery limbs, no
+ * randomness inside (blinding coefficients and the mask polynomial are inputs), no host work of size n or nnz per call.  PCDHIP_E_ARG
+ * for null pointers, mixed fields, counts beyond a buffer and the aliases each call forbids.  ark-marlin is not vendored: every call is
+ * specified by the formula written here.  Notation: H the domain of domain_h_n elements with the generator w of the resident
+ * transform, X its subdomain of domain_x_n elements, period = |H| / |X|, pi the `reindex_by_subdomain` of pcdhip_marlin_mats_upload,
+ * z the full assignment of num_cols elements in variable order (the first |X| the formatted public input; z[c] = 0 for c >= num_cols),
+ * v_S = X^|S| - 1.  Unless said otherwise a call only QUEUES its launches, as K9's do.
+ *
+ * pcdhip_marlin_mats_upload_ex: pcdhip_marlin_mats_upload with a choice of forms.  bit 0: the transposed matrices that
+ * pcdhip_marlin_t_evals needs (all that pcdhip_marlin_mats_upload makes: it is this call with forms = 1, and its handle holds the same
+ * memory and gives the same pcdhip_marlin_mats_info and results as before); bit 1: the forward A, B, C for pcdhip_marlin_zm_evals, laid
+ * out as the witness map's mat-vec takes them.  forms == 0 or any higher bit: PCDHIP_E_ARG.  pcdhip_marlin_t_evals on a handle without
+ * bit 0 and pcdhip_marlin_zm_evals on one without bit 1 return PCDHIP_E_ARG; pcdhip_marlin_mats_info speaks of the transposed form
+ * alone (no segments for a handle without it). */
+int pcdhip_marlin_mats_upload_ex(pcdhip_ctx* ctx, int field_id, const pcdhip_csr* A, const pcdhip_csr* B, const pcdhip_csr* C, size_t num_cols,
+                                 size_t domain_h_n, size_t domain_x_n, uint32_t forms, pcdhip_marlin_mats** out);
+/* z_M on H: out_M[r] = sum_{(r, c, v) in M} v z[c] for r < num_rows and out_M[r] = 0 for num_rows <= r < domain_h_n, M = A, B and
+ * (zc_out non-NULL) C; duplicate entries accumulate.  z: at least num_cols elements; outputs: at least domain_h_n each, distinct from z
+ * and from each other.  The witness map's mat-vec (one lane per short row, a wave per row of more than 16 entries, additions instead of
+ * products for the coefficients -32 .. 32) between two conversions of image; C is not computed when zc_out is NULL. */
+int pcdhip_marlin_zm_evals(pcdhip_ctx* ctx, const pcdhip_marlin_mats* mats, const pcdhip_buf* z, pcdhip_buf* za_out, pcdhip_buf* zb_out,
+                           pcdhip_buf* zc_out /* nullable */);
+/* z on H at pi's places, out[pi(c)] = z[c]: for k < domain_h_n, out[k] = z[k / period] when k % period == 0, else
+ * out[k] = z[domain_x_n + (k - k / period - 1)]; an index >= num_cols reads as 0.  period == 1 (X = H) is legal: out[k] = z[k].  A gather,
+ * one lane per k, no field arithmetic.  Both sizes must be domain sizes and domain_x_n divide domain_h_n; num_cols <= domain_h_n and
+ * <= z's elements; out at least domain_h_n elements and not z (PCDHIP_E_ARG otherwise). */
+int pcdhip_marlin_place_assignment(pcdhip_ctx* ctx, int field_id, size_t domain_h_n, size_t domain_x_n, const pcdhip_buf* z, size_t num_cols,
+                                   pcdhip_buf* out);
+/* Hiding: p <- p + b(X) (X^domain_n - 1) in place, b of k host coefficients (low degree first).  *out_len = max(len, domain_n + k); the
+ * coefficients from len up to that are taken as 0 first, and the buffer must hold *out_len elements.  k == 0 is a no-op: nothing is
+ * read or written and *out_len = len.  Only the two windows of k coefficients (and the zero tail) are touched, whatever len is; any
+ * domain_n >= 1 and any k (the windows may overlap).  Upstream's hiding uses k = 1.  WAITS for the device: b is the caller's memory. */
+int pcdhip_poly_add_vanishing_multiple(pcdhip_ctx* ctx, pcdhip_buf* p, size_t len, const uint64_t* blind_mont, size_t k, size_t domain_n,
+                                       size_t* out_len);
+/* The pointwise core of the first sumcheck, for i < n and eta_mont = eta_A, eta_B, eta_C:
+ *   q_i = r_alpha_i (eta_A za_i + eta_B zb_i + eta_C za_i zb_i) - t_i z_i
+ * computed as r (za (eta_A + eta_C zb) + eta_B zb) - t z in ONE launch, one lane per element: the five inputs are read once as ABI
+ * words, one store.  Aliasing: element i depends on element i of the inputs alone and is stored after they are read, so q_out may be
+ * any input's buffer.  Buffers never overlap in part, so a q_out that is two inputs' buffer means that those two inputs are the same
+ * vector, which is legal like any other repeated input; there is no alias this call refuses.  n == 0 succeeds without a launch. */
+int pcdhip_marlin_sumcheck1_q(pcdhip_ctx* ctx, const uint64_t* eta_mont /* 3 elements */, const pcdhip_buf* za, const pcdhip_buf* zb,
+                              const pcdhip_buf* r_alpha, const pcdhip_buf* t, const pcdhip_buf* z, size_t n, pcdhip_buf* q_out);
+/* Round 1 whole.  mats: a handle with the forward form; z: at least num_cols elements; blind_*_mont: k_w, k_a, k_b >= 0 host
+ * coefficients (0: not hiding; the pointer may then be NULL).  Coefficient vectors written, low degree first:
+ *   x_hat   = the inverse transform on X of z[0 .. |X|)                                      |X| coefficients
+ *   z_poly  = interp_H(place(z)) + b_w v_H      (place = pcdhip_marlin_place_assignment)     |H| + k_w
+ *   w       = (z_poly - x_hat) / v_X                                                         |H| + k_w - |X|   (0 for X = H, k_w = 0)
+ *   w_rem   = the remainder of that division, |X| coefficients: ZERO by construction (z_poly - x_hat vanishes on X); it is written so
+ *             that the caller can see it.  Since deg x_hat < |X|, w is the quotient of z_poly itself and w_rem its remainder less x_hat.
+ *   za_poly = interp_H(A z) + b_a v_H           zb_poly = interp_H(B z) + b_b v_H            |H| + k_a, |H| + k_b
+ * and, when za_evals / zb_evals are not NULL, z_A and z_B on H (|H| elements each, pcdhip_marlin_zm_evals).  out_lens = the lengths of
+ * x_hat, z_poly, w, za_poly, zb_poly; every buffer must hold its length (w may be NULL when its length is 0) and all buffers of the
+ * call are distinct.  The transforms are the library's general ones (H and X may be mixed-radix); workspace is the context's.  The
+ * call WAITS for the device before it returns: the blinding coefficients are the caller's memory. */
+int pcdhip_marlin_round1(pcdhip_ctx* ctx, const pcdhip_marlin_mats* mats, const pcdhip_buf* z, const uint64_t* blind_w_mont, size_t k_w,
+                         const uint64_t* blind_a_mont, size_t k_a, const uint64_t* blind_b_mont, size_t k_b, pcdhip_buf* x_hat,
+                         pcdhip_buf* z_poly, pcdhip_buf* w, pcdhip_buf* w_rem, pcdhip_buf* za_poly, pcdhip_buf* zb_poly,
+                         pcdhip_buf* za_evals /* nullable */, pcdhip_buf* zb_evals /* nullable */, size_t out_lens[5]);
+/* The first sumcheck whole: with r = r(alpha, X) (|H| coefficients, the interpolation of pcdhip_domain_bivariate_lagrange on H), t the
+ * interpolation of pcdhip_marlin_t_evals(eta, r on H), and s the mask polynomial (NULL: none),
+ *   q_1 = s + r (eta_A z_A + eta_B z_B + eta_C z_A z_B) - t z = h_1 v_H + X g_1 + sigma_1 / |H|
+ * mats: a handle with the transposed form; za_poly, zb_poly, z_poly with their lengths (each >= 1) as round 1 leaves them.  Steps: r
+ * and t on H, both to coefficients, the five polynomials z_A, z_B, r, t, z evaluated on D, pcdhip_marlin_sumcheck1_q there, the inverse
+ * transform on D, + s, the division by v_H.  Outputs: t_poly (|H| coefficients), h_1 (len_q - |H| coefficients, len_q = max(|H| + len_za
+ * + len_zb - 2, |H| + len_z - 1, len_mask): the quotient, its top coefficients zero when q_1 is shorter than that bound), g_1 (|H| - 1
+ * coefficients: the remainder shifted down by one), and sigma = the remainder's constant term in a one-element buffer -- sigma_1 / |H|,
+ * which is 0 for a satisfied system and a mask that sums to zero on H.  out_lens = the lengths of t_poly, h_1, g_1.  Outputs are
+ * distinct from each other and from the inputs; h_1 / g_1 may be NULL when their length is 0.
+ * D: domain_d_n == 0 means pcdhip_domain_size(field, |H| + len_za + len_zb - 2), the length of the longest product -- 3 |H| + k_a + k_b - 2
+ * after round 1.  This is upstream's `mul_domain` RESTATED FROM MEMORY, as K10's rule for |B| is; a caller that knows better passes its
+ * own n = 2^a q^b.  PCDHIP_E_SIZE_UNSUPPORTED for a size that is no such domain (or when the rule finds none), PCDHIP_E_ARG for one
+ * below len_q.  H and D may be mixed-radix.  The call only queues its work: nothing of the caller's host memory is read after it
+ * returns, and the results are there after pcdhip_sync or any call that waits. */
+int pcdhip_marlin_sumcheck1(pcdhip_ctx* ctx, const pcdhip_marlin_mats* mats, const uint64_t* eta_mont /* 3 elements */,
+                            const uint64_t* alpha_mont, const pcdhip_buf* za_poly, size_t len_za, const pcdhip_buf* zb_poly, size_t len_zb,
+                            const pcdhip_buf* z_poly, size_t len_z, const pcdhip_buf* mask /* nullable */, size_t len_mask,
+                            size_t domain_d_n /* 0: rule */, pcdhip_buf* t_poly, pcdhip_buf* h1, pcdhip_buf* g1, pcdhip_buf* sigma,
+                            size_t out_lens[3]);
+
 /* ---- timing helpers (HIP events on the context's stream, for bench.py) ------------------------- */
 int pcdhip_timer_start(pcdhip_ctx* ctx);
 int pcdhip_timer_stop(pcdhip_ctx* ctx, float* out_ms);

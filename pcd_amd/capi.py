@@ -81,6 +81,8 @@ EXPORTS = [
     "pcdhip_marlin_sumcheck_ab", "pcdhip_marlin_sumcheck_f",
     "pcdhip_marlin_index_build", "pcdhip_marlin_index_free", "pcdhip_marlin_index_info", "pcdhip_marlin_index_timings", "pcdhip_marlin_index_vec", "pcdhip_marlin_index_commit",
     "pcdhip_fft_general_dev", "pcdhip_poly_evals_on_domain",
+    "pcdhip_marlin_mats_upload_ex", "pcdhip_marlin_zm_evals", "pcdhip_marlin_place_assignment", "pcdhip_poly_add_vanishing_multiple",
+    "pcdhip_marlin_sumcheck1_q", "pcdhip_marlin_round1", "pcdhip_marlin_sumcheck1",
 ]
 
 
@@ -124,6 +126,13 @@ def lib():
         _LIB.pcdhip_marlin_index_commit.argtypes = [vp, vp, vp, vp, vp]
         _LIB.pcdhip_fft_general_dev.argtypes = [vp, vp, sz, C.c_int, C.c_int]
         _LIB.pcdhip_poly_evals_on_domain.argtypes = [vp, vp, sz, sz, C.c_int, vp]
+        _LIB.pcdhip_marlin_mats_upload_ex.argtypes = [vp, C.c_int, vp, vp, vp, sz, sz, sz, C.c_uint32, vp]
+        _LIB.pcdhip_marlin_zm_evals.argtypes = [vp, vp, vp, vp, vp, vp]
+        _LIB.pcdhip_marlin_place_assignment.argtypes = [vp, C.c_int, sz, sz, vp, sz, vp]
+        _LIB.pcdhip_poly_add_vanishing_multiple.argtypes = [vp, vp, sz, vp, sz, sz, szp]
+        _LIB.pcdhip_marlin_sumcheck1_q.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        _LIB.pcdhip_marlin_round1.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, szp]
+        _LIB.pcdhip_marlin_sumcheck1.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, sz, vp, vp, vp, vp, szp]
     return _LIB
 
 
@@ -721,7 +730,7 @@ class Context:
         h = C.c_void_p()
         self._check(lib().pcdhip_marlin_mats_upload(self._ctx, field, C.byref(A), C.byref(B), C.byref(Cm), num_cols, int(domain_h_n),
                                                     int(domain_x_n), C.byref(h)))
-        return MarlinMats(self, h, field, int(domain_h_n))
+        return MarlinMats(self, h, field, int(domain_h_n), int(domain_x_n), int(num_cols))
 
     def marlin_t_evals(self, mats, eta_mont, r_alpha, out=None):
         """t_out[j] = sum_M eta_M sum_{(r, c, v) in M, pi(c) = j} v r_alpha[r] for j < |H| -> out"""
@@ -776,6 +785,99 @@ class Context:
         self._check(lib().pcdhip_marlin_index_build(self._ctx, field, C.byref(A), C.byref(B), C.byref(Cm), num_cols, int(domain_h_n),
                                                     int(domain_x_n), int(domain_k_n), int(domain_b_n), int(keep), C.byref(h)))
         return MarlinIndex(self, h, field)
+
+    # ---- K11: round 1 and the first sumcheck
+    def marlin_mats_upload_ex(self, field, r1cs, domain_h_n, domain_x_n, forms, num_cols=None):
+        """marlin_mats_upload with a choice of forms: bit 0 the transposed matrices of marlin_t_evals, bit 1 the forward A, B, C of
+        marlin_zm_evals"""
+        A = self._csr(r1cs.rp_a, r1cs.col_a, r1cs.coeff_a)
+        B = self._csr(r1cs.rp_b, r1cs.col_b, r1cs.coeff_b)
+        Cm = self._csr(r1cs.rp_c, r1cs.col_c, r1cs.coeff_c)
+        num_cols = r1cs.num_vars if num_cols is None else int(num_cols)
+        h = C.c_void_p()
+        self._check(lib().pcdhip_marlin_mats_upload_ex(self._ctx, field, C.byref(A), C.byref(B), C.byref(Cm), num_cols, int(domain_h_n),
+                                                       int(domain_x_n), int(forms), C.byref(h)))
+        return MarlinMats(self, h, field, int(domain_h_n), int(domain_x_n), int(num_cols), int(forms))
+
+    def marlin_zm_evals(self, mats, z, za=None, zb=None, zc=None, want_c=True):
+        """z_M[r] = sum_{(r, c, v) in M} v z[c] on H, zeros from num_rows up -> (za, zb, zc); zc is None with want_c=False"""
+        own = []
+        outs = []
+        for o, want in ((za, True), (zb, True), (zc, want_c)):
+            if o is None and want:
+                o = self.buf_alloc(mats.field, mats.domain_h_n)
+                own.append(o)
+            outs.append(o)
+        self._call_into(own, lambda: lib().pcdhip_marlin_zm_evals(self._ctx, mats._h, z._h, outs[0]._h, outs[1]._h,
+                                                                  outs[2]._h if outs[2] is not None else None))
+        return tuple(outs)
+
+    def marlin_place_assignment(self, field, domain_h_n, domain_x_n, z, num_cols=None, out=None):
+        """out[pi(c)] = z[c] over the domain_h_n places of H, zeros where no variable sits -> out"""
+        num_cols = z.n if num_cols is None else int(num_cols)
+        own = [] if out is not None else [self.buf_alloc(field, int(domain_h_n))]
+        out = out if out is not None else own[0]
+        self._call_into(own, lambda: lib().pcdhip_marlin_place_assignment(self._ctx, field, int(domain_h_n), int(domain_x_n), z._h, num_cols,
+                                                                          out._h))
+        return out
+
+    def poly_add_vanishing_multiple(self, p, blind_mont, domain_n, length=None):
+        """p += b(X) (X^domain_n - 1) in place for the host coefficients b (k rows; None or empty: a no-op) -> the new length"""
+        length = p.n if length is None else int(length)
+        b = None if blind_mont is None else _u64(blind_mont).reshape(-1, FIELD_LIMBS[p.field])
+        k = 0 if b is None else b.shape[0]
+        n = C.c_size_t(0)
+        self._check(lib().pcdhip_poly_add_vanishing_multiple(self._ctx, p._h, length, _p(b) if k else None, k, int(domain_n), C.byref(n)))
+        return n.value
+
+    def marlin_sumcheck1_q(self, eta_mont, za, zb, r_alpha, t, z, n=None, out=None):
+        """q_i = r_i (eta_A za_i + eta_B zb_i + eta_C za_i zb_i) - t_i z_i for i < n -> out (allocated when not passed; may be an input)"""
+        n = min(x.n for x in (za, zb, r_alpha, t, z)) if n is None else int(n)
+        own = [] if out is not None else [self.buf_alloc(za.field, n)]
+        out = out if out is not None else own[0]
+        eta = _u64(eta_mont).reshape(3, FIELD_LIMBS[za.field])
+        self._call_into(own, lambda: lib().pcdhip_marlin_sumcheck1_q(self._ctx, _p(eta), za._h, zb._h, r_alpha._h, t._h, z._h, n, out._h))
+        return out
+
+    def marlin_round1(self, mats, z, blind_w=None, blind_a=None, blind_b=None, want_evals=False):
+        """round 1 over a handle with the forward form: z (DeviceBuf of num_cols elements) and the host blinding coefficients of w, z_A,
+        z_B (rows of ABI limbs; None: not hiding) -> dict of DeviceBufs x_hat, z_poly, w (None when empty), w_rem, za_poly, zb_poly, (with
+        want_evals) za_evals, zb_evals, and "lens": the lengths of x_hat, z_poly, w, za_poly, zb_poly"""
+        f, h_n, x_n = mats.field, mats.domain_h_n, mats.domain_x_n
+        bl = [None if b is None else _u64(b).reshape(-1, FIELD_LIMBS[f]) for b in (blind_w, blind_a, blind_b)]
+        k = [0 if b is None else b.shape[0] for b in bl]
+        sizes = {"x_hat": x_n, "z_poly": h_n + k[0], "w": h_n + k[0] - x_n, "w_rem": x_n, "za_poly": h_n + k[1], "zb_poly": h_n + k[2]}
+        if want_evals:
+            sizes.update(za_evals=h_n, zb_evals=h_n)
+        out = {name: (self.buf_alloc(f, n) if n else None) for name, n in sizes.items()}
+        hd = lambda name: out[name]._h if out.get(name) is not None else None
+        lens = (C.c_size_t * 5)()
+        self._call_into([b for b in out.values() if b is not None], lambda: lib().pcdhip_marlin_round1(
+            self._ctx, mats._h, z._h, _p(bl[0]) if k[0] else None, k[0], _p(bl[1]) if k[1] else None, k[1], _p(bl[2]) if k[2] else None, k[2],
+            hd("x_hat"), hd("z_poly"), hd("w"), hd("w_rem"), hd("za_poly"), hd("zb_poly"), hd("za_evals"), hd("zb_evals"), lens))
+        out["lens"] = [int(v) for v in lens]
+        return out
+
+    def marlin_sumcheck1(self, mats, eta_mont, alpha_mont, za_poly, zb_poly, z_poly, len_za=None, len_zb=None, len_z=None, mask=None,
+                         len_mask=None, domain_d_n=0):
+        """the first sumcheck over a handle with the transposed form -> dict of DeviceBufs t_poly, h1 (None when empty), g1 (None when
+        empty), sigma (one element: the remainder's constant term) and "lens": the lengths of t_poly, h1, g1"""
+        f, h_n = mats.field, mats.domain_h_n
+        len_za = za_poly.n if len_za is None else int(len_za)
+        len_zb = zb_poly.n if len_zb is None else int(len_zb)
+        len_z = z_poly.n if len_z is None else int(len_z)
+        len_mask = 0 if mask is None else (mask.n if len_mask is None else int(len_mask))
+        q_len = max(h_n + len_za + len_zb - 2, h_n + len_z - 1, len_mask)
+        sizes = {"t_poly": h_n, "h1": max(q_len - h_n, 0), "g1": h_n - 1, "sigma": 1}
+        out = {name: (self.buf_alloc(f, n) if n else None) for name, n in sizes.items()}
+        hd = lambda name: out[name]._h if out[name] is not None else None
+        lens = (C.c_size_t * 3)()
+        eta = _u64(eta_mont).reshape(3, FIELD_LIMBS[f])
+        self._call_into([b for b in out.values() if b is not None], lambda: lib().pcdhip_marlin_sumcheck1(
+            self._ctx, mats._h, _p(eta), _p(_u64(alpha_mont)), za_poly._h, len_za, zb_poly._h, len_zb, z_poly._h, len_z,
+            mask._h if mask is not None else None, len_mask, int(domain_d_n), hd("t_poly"), hd("h1"), hd("g1"), hd("sigma"), lens))
+        out["lens"] = [int(v) for v in lens]
+        return out
 
     def fft_general_dev(self, data, n=None, inverse=False, coset=False):
         """pcdhip_fft_general on the first n (default: all) elements of a DeviceBuf, in place; n = 2^a q^b"""
@@ -962,8 +1064,9 @@ class DeviceBuf:
 
 
 class MarlinMats:
-    def __init__(self, ctx, h, field, domain_h_n):
+    def __init__(self, ctx, h, field, domain_h_n, domain_x_n=None, num_cols=None, forms=1):
         self.ctx, self._h, self.field, self.domain_h_n = ctx, h, field, domain_h_n
+        self.domain_x_n, self.num_cols, self.forms = domain_x_n, num_cols, forms
 
     def info(self):
         """{"seg_len", "segments", "long_outputs", "launches"} of this handle (pcdhip_marlin_mats_info)"""

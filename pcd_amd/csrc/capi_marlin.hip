@@ -2,7 +2,8 @@
 // (marlin.hip.h and the t(X) kernels of inst_field.hip: r(alpha, .) on H, the transposed mat-vec behind t(X), the rational sumcheck).
 // Every call queues its launches on the context's stream and returns: nothing here waits for the device except the upload of the matrices.
 // K10, the index on device (the arithmetisation onto K, the coefficients, the evaluations on B, the twelve commitments), follows below;
-// pcdhip_marlin_index_build waits for its own uploads and for the end of its work.
+// pcdhip_marlin_index_build waits for its own uploads and for the end of its work.  K11 at the end: round 1 (the assignment on H, z_A and
+// z_B over the forward matrices, w) and the first sumcheck (q in one launch, h_1 and g_1).
 #include <stdlib.h>
 
 #include "capi_internal.h"
@@ -10,7 +11,8 @@
 using namespace pcd;
 
 namespace {
-enum { AUX_MARLIN_PART = AUX_FB_OUT + 5, AUX_MARLIN_A, AUX_MARLIN_B };
+// (AUX_MARLIN_WS: the vectors of a K11 driver in one block; AUX_MARLIN_BLIND: the blinding coefficients of a call, staged from the host)
+enum { AUX_MARLIN_PART = AUX_FB_OUT + 5, AUX_MARLIN_A, AUX_MARLIN_B, AUX_MARLIN_WS, AUX_MARLIN_BLIND };
 const size_t kMaxLen = (size_t)1 << 31;
 
 bool is_domain_size(int field_id, size_t n) { return n != 0 && n < kMaxLen && pcdhip_domain_size(field_id, n) == n; }
@@ -48,6 +50,100 @@ bool is_input(const SumcheckArgs& a, const uint32_t* p) {
   for (int m = 0; m < 3; m++) if (p == a.row[m] || p == a.col[m] || p == a.val[m] || (a.rc[m] && p == a.rc[m])) return true;
   return false;
 }
+void mats_release(pcdhip_marlin_mats* h) {
+  if (h->dev) (void)hipFree(h->dev);
+  if (h->dev_fwd) (void)hipFree(h->dev_fwd);
+  delete h;
+}
+// bit 0 of a handle's forms: the three matrices transposed, their rows at pi's places, and the segment tables of the long rows
+int upload_transposed(pcdhip_ctx* ctx, const FieldEntry& fe, const pcdhip_csr* const ms[3], pcdhip_marlin_mats* h) {
+  const size_t domain_h_n = h->domain_h_n, domain_x_n = h->domain_x_n, num_cols = h->num_cols, rows = h->num_rows;
+  const size_t limbs = (size_t)fe.abi_words / 2, period = domain_h_n / domain_x_n;
+  // segment length of the long rows: MARLIN_T_SEG, or the tuning knob PCDHIP_MARLIN_SEG (64 .. 2^20) read at upload
+  uint32_t seg_len = MARLIN_T_SEG;
+  if (const char* e = getenv("PCDHIP_MARLIN_SEG")) { const long v = atol(e); if (v >= 64 && v <= (1 << 20)) seg_len = (uint32_t)v; }
+  std::vector<uint32_t> perm(num_cols);
+  for (size_t c = 0; c < num_cols; c++) perm[c] = (uint32_t)reindex(c, domain_x_n, period);
+  // (num_cols <= |H| keeps every image below |H|: pi maps [0, |H|) onto itself)
+  HostCsrT tr[3];
+  size_t total = 0, base[3], off[6];
+  for (int k = 0; k < 3; k++) {
+    int rc = transpose_csr(ms[k], num_cols, limbs, &tr[k], perm.data(), domain_h_n);
+    if (rc) return rc;
+    base[k] = total;
+    total += csr_bytes(&tr[k].view, fe, off) + 64;
+  }
+  // the segments of the rows that a lane does not serve, by (row, matrix)
+  std::vector<MarlinSeg> segs;
+  std::vector<uint32_t> long_out, long_seg_lo;
+  for (size_t j = 0; j < domain_h_n; j++) {
+    bool any = false;
+    for (uint32_t k = 0; k < 3; k++) {
+      const uint64_t lo = tr[k].rp[j], hi = tr[k].rp[j + 1];
+      if (hi - lo <= SPMV_LONG_ROW) continue;
+      if (!any) { long_out.push_back((uint32_t)j); long_seg_lo.push_back((uint32_t)segs.size()); any = true; }
+      for (uint64_t s = lo; s < hi; s += seg_len) segs.push_back({k, (uint32_t)j, s, std::min<uint64_t>(hi, s + seg_len)});
+    }
+  }
+  if (segs.size() >> 31) return PCDHIP_E_ARG;
+  long_seg_lo.push_back((uint32_t)segs.size());
+  const size_t seg_off = total, lo_off = seg_off + segs.size() * sizeof(MarlinSeg), sl_off = lo_off + (long_out.size() + 2) / 2 * 8;
+  total = sl_off + (long_seg_lo.size() + 2) / 2 * 8;
+  h->seg_len = seg_len;
+  hipError_t e = hipMalloc(&h->dev, total + 64);
+  if (e != hipSuccess) { h->dev = nullptr; return fail(ctx, e); }
+  char* d = (char*)h->dev;
+  int rc = PCDHIP_OK;
+  for (int k = 0; k < 3 && !rc; k++) rc = upload_csr_to(ctx, &tr[k].view, fe, std::max<size_t>(rows, 1), d + base[k], &h->view.m[k]);
+  if (!rc && !segs.empty()) {
+    e = hipMemcpyAsync(d + seg_off, segs.data(), segs.size() * sizeof(MarlinSeg), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + lo_off, long_out.data(), long_out.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + sl_off, long_seg_lo.data(), long_seg_lo.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the host vectors above are done with
+    if (e != hipSuccess) rc = fail(ctx, e);
+  }
+  if (rc) return rc;
+  h->view.rows = (uint32_t)domain_h_n;
+  h->view.segs = (const MarlinSeg*)(d + seg_off); h->view.n_segs = (uint32_t)segs.size();
+  h->view.long_out = (const uint32_t*)(d + lo_off); h->view.long_seg_lo = (const uint32_t*)(d + sl_off);
+  h->view.n_long_out = (uint32_t)long_out.size();
+  return PCDHIP_OK;
+}
+// bit 1: the forward A, B, C as the witness map's mat-vec takes them (upload_csr_to: small coefficients first in a row, long rows listed)
+int upload_forward(pcdhip_ctx* ctx, const FieldEntry& fe, const pcdhip_csr* const ms[3], pcdhip_marlin_mats* h) {
+  size_t base[3], total = 0, off[6];
+  for (int k = 0; k < 3; k++) { base[k] = total; total += csr_bytes(ms[k], fe, off) + 64; }
+  hipError_t e = hipMalloc(&h->dev_fwd, total + 64);
+  if (e != hipSuccess) { h->dev_fwd = nullptr; return fail(ctx, e); }
+  for (int k = 0; k < 3; k++) {
+    int rc = upload_csr_to(ctx, ms[k], fe, h->num_cols, (char*)h->dev_fwd + base[k], &h->fwd[k]);
+    if (rc) return rc;
+  }
+  return PCDHIP_OK;
+}
+// r(x, .) over the domain of n elements into out (n ABI elements on the device); the caller has bound the device and checked n
+int lagrange_dev(pcdhip_ctx* ctx, int field_id, size_t n, const uint64_t* x_mont, uint32_t* out) {
+  const FieldEntry& fe = field_entry(field_id);
+  if (n == 1) {
+    TRY(fe.marlin_lagrange(ctx->stream, nullptr, nullptr, 1, (const uint32_t*)x_mont, 1, out));
+    return PCDHIP_OK;
+  }
+  Dom d;
+  int rc = pick_domain(field_id, n, &d);
+  if (rc) return rc;
+  const FftTables* t;
+  rc = d.m == 1 ? get_tables(ctx, field_id, d.a, &t) : get_mixed_tables(ctx, field_id, d, &t);
+  if (rc) return rc;
+  TRY(fe.marlin_lagrange(ctx->stream, t->consts, t->tw_fwd, d.n / d.m, (const uint32_t*)x_mont, d.n, out));
+  return PCDHIP_OK;
+}
+// t on H from r_alpha (num_rows elements) into t_out (|H| elements), both ABI on the device and distinct
+int t_evals_dev(pcdhip_ctx* ctx, const pcdhip_marlin_mats* mats, const uint64_t* eta_mont, const uint32_t* r_alpha, uint32_t* t_out) {
+  const FieldEntry& fe = field_entry(mats->field_id);
+  TRY(ctx->aux_ws.ensure(AUX_MARLIN_PART, std::max<size_t>(mats->view.n_segs, 1) * fe.words * 4));
+  TRY(fe.marlin_t_evals(ctx->stream, mats->view, (const uint32_t*)eta_mont, r_alpha, (uint32_t*)ctx->aux_ws.buf[AUX_MARLIN_PART], t_out, nullptr));
+  return PCDHIP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -57,24 +153,17 @@ int pcdhip_domain_bivariate_lagrange(pcdhip_ctx* ctx, int field_id, size_t domai
   if (!is_domain_size(field_id, domain_n)) return PCDHIP_E_SIZE_UNSUPPORTED;
   if (domain_n > out->n) return PCDHIP_E_ARG;
   BIND();
-  const FieldEntry& fe = field_entry(field_id);
-  if (domain_n == 1) {
-    TRY(fe.marlin_lagrange(ctx->stream, nullptr, nullptr, 1, (const uint32_t*)x_mont, 1, out->dptr));
-    return PCDHIP_OK;
-  }
-  Dom d;
-  int rc = pick_domain(field_id, domain_n, &d);
-  if (rc) return rc;
-  const FftTables* t;
-  rc = d.m == 1 ? get_tables(ctx, field_id, d.a, &t) : get_mixed_tables(ctx, field_id, d, &t);
-  if (rc) return rc;
-  TRY(fe.marlin_lagrange(ctx->stream, t->consts, t->tw_fwd, d.n / d.m, (const uint32_t*)x_mont, d.n, out->dptr));
-  return PCDHIP_OK;
+  return lagrange_dev(ctx, field_id, domain_n, x_mont, out->dptr);
 }
 
 int pcdhip_marlin_mats_upload(pcdhip_ctx* ctx, int field_id, const pcdhip_csr* A, const pcdhip_csr* B, const pcdhip_csr* C, size_t num_cols,
                               size_t domain_h_n, size_t domain_x_n, pcdhip_marlin_mats** out) {
-  if (!ctx || !valid_field(field_id) || !A || !B || !C || !out) return PCDHIP_E_ARG;
+  return pcdhip_marlin_mats_upload_ex(ctx, field_id, A, B, C, num_cols, domain_h_n, domain_x_n, 1u, out);
+}
+
+int pcdhip_marlin_mats_upload_ex(pcdhip_ctx* ctx, int field_id, const pcdhip_csr* A, const pcdhip_csr* B, const pcdhip_csr* C, size_t num_cols,
+                                 size_t domain_h_n, size_t domain_x_n, uint32_t forms, pcdhip_marlin_mats** out) {
+  if (!ctx || !valid_field(field_id) || !A || !B || !C || !out || forms == 0 || forms > 3) return PCDHIP_E_ARG;
   if (!is_domain_size(field_id, domain_h_n) || !is_domain_size(field_id, domain_x_n) || domain_h_n % domain_x_n != 0) return PCDHIP_E_ARG;
   if (A->num_rows != B->num_rows || A->num_rows != C->num_rows || A->num_rows > domain_h_n || num_cols > domain_h_n) return PCDHIP_E_ARG;
   const pcdhip_csr* ms[3] = {A, B, C};
@@ -82,57 +171,13 @@ int pcdhip_marlin_mats_upload(pcdhip_ctx* ctx, int field_id, const pcdhip_csr* A
   BIND();
   return guarded([&]() -> int {
     const FieldEntry& fe = field_entry(field_id);
-    const size_t limbs = (size_t)fe.abi_words / 2, period = domain_h_n / domain_x_n, rows = A->num_rows;
-    // segment length of the long rows: MARLIN_T_SEG, or the tuning knob PCDHIP_MARLIN_SEG (64 .. 2^20) read at upload
-    uint32_t seg_len = MARLIN_T_SEG;
-    if (const char* e = getenv("PCDHIP_MARLIN_SEG")) { const long v = atol(e); if (v >= 64 && v <= (1 << 20)) seg_len = (uint32_t)v; }
-    std::vector<uint32_t> perm(num_cols);
-    for (size_t c = 0; c < num_cols; c++) perm[c] = (uint32_t)reindex(c, domain_x_n, period);
-    // (num_cols <= |H| keeps every image below |H|: pi maps [0, |H|) onto itself)
-    HostCsrT tr[3];
-    size_t total = 0, base[3], off[6];
-    for (int k = 0; k < 3; k++) {
-      int rc = transpose_csr(ms[k], num_cols, limbs, &tr[k], perm.data(), domain_h_n);
-      if (rc) return rc;
-      base[k] = total;
-      total += csr_bytes(&tr[k].view, fe, off) + 64;
-    }
-    // the segments of the rows that a lane does not serve, by (row, matrix)
-    std::vector<MarlinSeg> segs;
-    std::vector<uint32_t> long_out, long_seg_lo;
-    for (size_t j = 0; j < domain_h_n; j++) {
-      bool any = false;
-      for (uint32_t k = 0; k < 3; k++) {
-        const uint64_t lo = tr[k].rp[j], hi = tr[k].rp[j + 1];
-        if (hi - lo <= SPMV_LONG_ROW) continue;
-        if (!any) { long_out.push_back((uint32_t)j); long_seg_lo.push_back((uint32_t)segs.size()); any = true; }
-        for (uint64_t s = lo; s < hi; s += seg_len) segs.push_back({k, (uint32_t)j, s, std::min<uint64_t>(hi, s + seg_len)});
-      }
-    }
-    if (segs.size() >> 31) return PCDHIP_E_ARG;
-    long_seg_lo.push_back((uint32_t)segs.size());
-    const size_t seg_off = total, lo_off = seg_off + segs.size() * sizeof(MarlinSeg), sl_off = lo_off + (long_out.size() + 2) / 2 * 8;
-    total = sl_off + (long_seg_lo.size() + 2) / 2 * 8;
+    const size_t rows = A->num_rows;
     pcdhip_marlin_mats* h = new pcdhip_marlin_mats();
     h->field_id = field_id; h->domain_h_n = domain_h_n; h->domain_x_n = domain_x_n; h->num_rows = rows; h->num_cols = num_cols;
-    h->seg_len = seg_len;
-    hipError_t e = hipMalloc(&h->dev, total + 64);
-    if (e != hipSuccess) { delete h; return fail(ctx, e); }
-    char* d = (char*)h->dev;
-    int rc = PCDHIP_OK;
-    for (int k = 0; k < 3 && !rc; k++) rc = upload_csr_to(ctx, &tr[k].view, fe, std::max<size_t>(rows, 1), d + base[k], &h->view.m[k]);
-    if (!rc && !segs.empty()) {
-      e = hipMemcpyAsync(d + seg_off, segs.data(), segs.size() * sizeof(MarlinSeg), hipMemcpyHostToDevice, ctx->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(d + lo_off, long_out.data(), long_out.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(d + sl_off, long_seg_lo.data(), long_seg_lo.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the host vectors above are done with
-      if (e != hipSuccess) rc = fail(ctx, e);
-    }
-    if (rc) { (void)hipFree(h->dev); delete h; return rc; }
-    h->view.rows = (uint32_t)domain_h_n;
-    h->view.segs = (const MarlinSeg*)(d + seg_off); h->view.n_segs = (uint32_t)segs.size();
-    h->view.long_out = (const uint32_t*)(d + lo_off); h->view.long_seg_lo = (const uint32_t*)(d + sl_off);
-    h->view.n_long_out = (uint32_t)long_out.size();
+    h->forms = forms;
+    int rc = (forms & 1) ? upload_transposed(ctx, fe, ms, h) : PCDHIP_OK;
+    if (!rc && (forms & 2)) rc = upload_forward(ctx, fe, ms, h);
+    if (rc) { mats_release(h); return rc; }
     *out = h;
     return PCDHIP_OK;
   });
@@ -141,8 +186,7 @@ int pcdhip_marlin_mats_upload(pcdhip_ctx* ctx, int field_id, const pcdhip_csr* A
 void pcdhip_marlin_mats_free(pcdhip_ctx* ctx, pcdhip_marlin_mats* mats) {
   if (!mats) return;
   if (ctx) (void)hipSetDevice(ctx->device);
-  if (mats->dev) (void)hipFree(mats->dev);
-  delete mats;
+  mats_release(mats);
 }
 
 int pcdhip_marlin_mats_info(const pcdhip_marlin_mats* mats, uint64_t out[4]) {
@@ -155,13 +199,9 @@ int pcdhip_marlin_mats_info(const pcdhip_marlin_mats* mats, uint64_t out[4]) {
 int pcdhip_marlin_t_evals(pcdhip_ctx* ctx, const pcdhip_marlin_mats* mats, const uint64_t* eta_mont, const pcdhip_buf* r_alpha, pcdhip_buf* t_out) {
   if (!ctx || !mats || !eta_mont || !r_alpha || !t_out) return PCDHIP_E_ARG;
   if (r_alpha->field_id != mats->field_id || t_out->field_id != mats->field_id || r_alpha->dptr == t_out->dptr) return PCDHIP_E_ARG;
-  if (r_alpha->n < mats->num_rows || t_out->n < mats->domain_h_n) return PCDHIP_E_ARG;
+  if (r_alpha->n < mats->num_rows || t_out->n < mats->domain_h_n || !(mats->forms & 1)) return PCDHIP_E_ARG;
   BIND();
-  const FieldEntry& fe = field_entry(mats->field_id);
-  TRY(ctx->aux_ws.ensure(AUX_MARLIN_PART, std::max<size_t>(mats->view.n_segs, 1) * fe.words * 4));
-  TRY(fe.marlin_t_evals(ctx->stream, mats->view, (const uint32_t*)eta_mont, r_alpha->dptr, (uint32_t*)ctx->aux_ws.buf[AUX_MARLIN_PART],
-                        t_out->dptr, nullptr));
-  return PCDHIP_OK;
+  return t_evals_dev(ctx, mats, eta_mont, r_alpha->dptr, t_out->dptr);
 }
 
 int pcdhip_marlin_sumcheck_ab(pcdhip_ctx* ctx, const uint64_t* alpha_mont, const uint64_t* beta_mont, const uint64_t* coeff_mont,
@@ -420,6 +460,245 @@ int pcdhip_marlin_index_commit(pcdhip_ctx* ctx, const pcdhip_marlin_index* index
     items[4 * m + q].len = index->domain_k_n;
   }
   return pcdhip_kzg_commit(ctx, powers_of_g, nullptr, nullptr, items, 12, comm_xy, comm_inf, nullptr, nullptr, nullptr);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ K11: round 1 and the first sumcheck
+namespace {
+// `len` ABI elements of src -> the device image over the domain d with a zero tail -> the forward or inverse transform -> the first
+// out_n elements back as ABI words into dst (dst may be src: the vector sits in the workspace in between).  A domain of one element
+// has the identity for both transforms.
+int transform_abi(pcdhip_ctx* ctx, int field_id, const Dom& d, const uint32_t* src, size_t len, uint32_t* dst, size_t out_n, int inverse) {
+  const FieldEntry& fe = field_entry(field_id);
+  const size_t vb = (size_t)d.n * fe.words * 4;
+  TRY(ctx->aux_ws.ensure(AUX_FFT_X, vb));
+  TRY(ctx->aux_ws.ensure(AUX_FFT_TMP, vb));
+  uint32_t* x = (uint32_t*)ctx->aux_ws.buf[AUX_FFT_X];
+  TRY(fe.convert(ctx->stream, src, x, (uint32_t)len, 0));
+  if (len < d.n) TRY(hipMemsetAsync(x + len * fe.words, 0, (d.n - len) * fe.words * 4, ctx->stream));
+  if (d.n > 1) {
+    int rc = domain_transform(ctx, field_id, d, x, (uint32_t*)ctx->aux_ws.buf[AUX_FFT_TMP], inverse, 0, nullptr, nullptr);
+    if (rc) return rc;
+  }
+  TRY(fe.convert(ctx->stream, x, dst, (uint32_t)out_n, 1));
+  return PCDHIP_OK;
+}
+// M z on H for the forward matrices of a handle: z (num_cols ABI elements) -> the device image, the witness map's mat-vecs without
+// their input rows (spmv3 for all three, two spmv when C is not asked for: zero tails up to |H| included), -> out[M] as ABI words
+int zm_evals_dev(pcdhip_ctx* ctx, const pcdhip_marlin_mats* mats, const uint32_t* z_abi, uint32_t* const out[3]) {
+  const FieldEntry& fe = field_entry(mats->field_id);
+  const size_t h_n = mats->domain_h_n, ew = h_n * fe.words;
+  TRY(ctx->aux_ws.ensure(AUX_Z, std::max<size_t>(mats->num_cols, 1) * fe.words * 4));
+  TRY(ctx->aux_ws.ensure(AUX_A, 3 * ew * 4));
+  uint32_t *zd = (uint32_t*)ctx->aux_ws.buf[AUX_Z], *v = (uint32_t*)ctx->aux_ws.buf[AUX_A];
+  TRY(fe.convert(ctx->stream, z_abi, zd, (uint32_t)mats->num_cols, 0));
+  if (out[2]) TRY(fe.spmv3(ctx->stream, mats->fwd, zd, 0, (uint32_t)h_n, v, ew));
+  else for (int k = 0; k < 2; k++) TRY(fe.spmv(ctx->stream, mats->fwd[k], zd, 0, 0, (uint32_t)h_n, v + k * ew));
+  for (int k = 0; k < 3; k++) if (out[k]) TRY(fe.convert(ctx->stream, v + k * ew, out[k], (uint32_t)h_n, 1));
+  return PCDHIP_OK;
+}
+// p (len coefficients, room for max(len, n + k)) += blind (X^n - 1); blind: k coefficients on the host, staged at element `at` of
+// AUX_MARLIN_BLIND (which the caller has sized: several calls of one driver are queued before the stream is waited for)
+int add_vanishing_dev(pcdhip_ctx* ctx, const FieldEntry& fe, uint32_t* p, size_t len, const uint64_t* blind, size_t k, size_t n, size_t at) {
+  if (k == 0) return PCDHIP_OK;
+  const size_t eb = (size_t)fe.abi_words * 4;
+  uint32_t* bd = (uint32_t*)((char*)ctx->aux_ws.buf[AUX_MARLIN_BLIND] + at * eb);
+  TRY(hipMemcpyAsync(bd, blind, k * eb, hipMemcpyHostToDevice, ctx->stream));
+  if (len < n + k) TRY(hipMemsetAsync((char*)p + len * eb, 0, (n + k - len) * eb, ctx->stream));
+  TRY(fe.poly_add_vanishing(ctx->stream, p, bd, k, n));
+  return PCDHIP_OK;
+}
+// p = q (X^n - 1) + r for a SMALL n (round 1 divides |H| + k coefficients by v_X, and |X| is a handful of public inputs): the K8
+// kernel gives every lane its whole stride-n column of p, len / n terms, which is a quadratic cost here (2^20 lanes of 2^18 terms).
+// Instead the strided suffix sums S_m = sum_{i >= 0} p_(m + i n) by doubling -- S <- S + (S shifted down by n 2^t), log2(len / n)
+// passes of one addition per element between two workspace vectors (a pass may not run in place: it reads what another lane
+// writes) -- and then q_j = S_(j + n), r_j = S_j.  ws: two vectors of len elements.  Up to kDivDirect terms per lane the K8 kernel
+// is the cheaper one and is used as it stands.
+const size_t kDivDirect = 64;
+int div_vanishing_small_n(pcdhip_ctx* ctx, const FieldEntry& fe, const uint32_t* p, size_t len, size_t n, uint32_t* q, uint32_t* r,
+                          uint32_t* ws) {
+  if (len <= n * kDivDirect) {
+    TRY(fe.poly_div_vanishing(ctx->stream, p, len, n, q, r));
+    return PCDHIP_OK;
+  }
+  const size_t aw = fe.abi_words, eb = aw * 4;
+  const uint32_t* cur = p;
+  uint32_t* next = ws;
+  for (size_t off = n; off < len; off *= 2) {
+    TRY(fe.vec_addsub(ctx->stream, cur, cur + off * aw, len - off, 0, next));
+    TRY(hipMemcpyAsync(next + (len - off) * aw, cur + (len - off) * aw, off * eb, hipMemcpyDeviceToDevice, ctx->stream));
+    cur = next;
+    next = next == ws ? ws + len * aw : ws;
+  }
+  TRY(hipMemcpyAsync(q, cur + n * aw, (len - n) * eb, hipMemcpyDeviceToDevice, ctx->stream));
+  TRY(hipMemcpyAsync(r, cur, n * eb, hipMemcpyDeviceToDevice, ctx->stream));
+  return PCDHIP_OK;
+}
+bool same_field(int f, std::initializer_list<const pcdhip_buf*> bufs) {
+  for (const pcdhip_buf* b : bufs) if (b && b->field_id != f) return false;
+  return true;
+}
+// no two of the non-null buffers share their memory
+bool all_distinct(std::initializer_list<const pcdhip_buf*> bufs) {
+  for (auto a = bufs.begin(); a != bufs.end(); ++a)
+    for (auto b = a + 1; b != bufs.end(); ++b) if (*a && *b && (*a)->dptr == (*b)->dptr) return false;
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+int pcdhip_marlin_zm_evals(pcdhip_ctx* ctx, const pcdhip_marlin_mats* mats, const pcdhip_buf* z, pcdhip_buf* za_out, pcdhip_buf* zb_out,
+                           pcdhip_buf* zc_out) {
+  if (!ctx || !mats || !z || !za_out || !zb_out || !(mats->forms & 2)) return PCDHIP_E_ARG;
+  if (!same_field(mats->field_id, {z, za_out, zb_out, zc_out}) || !all_distinct({z, za_out, zb_out, zc_out})) return PCDHIP_E_ARG;
+  if (z->n < mats->num_cols || za_out->n < mats->domain_h_n || zb_out->n < mats->domain_h_n || (zc_out && zc_out->n < mats->domain_h_n))
+    return PCDHIP_E_ARG;
+  BIND();
+  uint32_t* const out[3] = {za_out->dptr, zb_out->dptr, zc_out ? zc_out->dptr : nullptr};
+  return zm_evals_dev(ctx, mats, z->dptr, out);
+}
+
+int pcdhip_marlin_place_assignment(pcdhip_ctx* ctx, int field_id, size_t domain_h_n, size_t domain_x_n, const pcdhip_buf* z, size_t num_cols,
+                                   pcdhip_buf* out) {
+  if (!ctx || !valid_field(field_id) || !z || !out || !same_field(field_id, {z, out}) || z->dptr == out->dptr) return PCDHIP_E_ARG;
+  if (!is_domain_size(field_id, domain_h_n) || !is_domain_size(field_id, domain_x_n) || domain_h_n % domain_x_n != 0) return PCDHIP_E_ARG;
+  if (num_cols > z->n || num_cols > domain_h_n || domain_h_n > out->n) return PCDHIP_E_ARG;
+  BIND();
+  TRY(field_entry(field_id).marlin_place(ctx->stream, z->dptr, num_cols, domain_x_n, domain_h_n, out->dptr));
+  return PCDHIP_OK;
+}
+
+int pcdhip_poly_add_vanishing_multiple(pcdhip_ctx* ctx, pcdhip_buf* p, size_t len, const uint64_t* blind_mont, size_t k, size_t domain_n,
+                                       size_t* out_len) {
+  if (!ctx || !p || !out_len || (k && !blind_mont) || domain_n == 0 || domain_n >= kMaxLen || k >= kMaxLen || len > p->n) return PCDHIP_E_ARG;
+  const size_t ol = k ? std::max(len, domain_n + k) : len;
+  if (ol > p->n) return PCDHIP_E_ARG;
+  *out_len = ol;
+  if (k == 0) return PCDHIP_OK;
+  BIND();
+  const FieldEntry& fe = field_entry(p->field_id);
+  TRY(ctx->aux_ws.ensure(AUX_MARLIN_BLIND, k * fe.abi_words * 4));
+  int rc = add_vanishing_dev(ctx, fe, p->dptr, len, blind_mont, k, domain_n, 0);
+  if (rc) return rc;
+  TRY(hipStreamSynchronize(ctx->stream));  // blind_mont is the caller's memory
+  return PCDHIP_OK;
+}
+
+int pcdhip_marlin_sumcheck1_q(pcdhip_ctx* ctx, const uint64_t* eta_mont, const pcdhip_buf* za, const pcdhip_buf* zb, const pcdhip_buf* r_alpha,
+                              const pcdhip_buf* t, const pcdhip_buf* z, size_t n, pcdhip_buf* q_out) {
+  if (!ctx || !eta_mont || !za || !zb || !r_alpha || !t || !z || !q_out || n >= kMaxLen) return PCDHIP_E_ARG;
+  if (!same_field(q_out->field_id, {za, zb, r_alpha, t, z})) return PCDHIP_E_ARG;
+  for (const pcdhip_buf* b : {za, zb, r_alpha, t, z, (const pcdhip_buf*)q_out}) if (n > b->n) return PCDHIP_E_ARG;
+  if (n == 0) return PCDHIP_OK;
+  BIND();
+  TRY(field_entry(q_out->field_id).marlin_sumcheck1_q(ctx->stream, (const uint32_t*)eta_mont, za->dptr, zb->dptr, r_alpha->dptr, t->dptr, z->dptr,
+                                                       n, q_out->dptr));
+  return PCDHIP_OK;
+}
+
+int pcdhip_marlin_round1(pcdhip_ctx* ctx, const pcdhip_marlin_mats* mats, const pcdhip_buf* z, const uint64_t* blind_w_mont, size_t k_w,
+                         const uint64_t* blind_a_mont, size_t k_a, const uint64_t* blind_b_mont, size_t k_b, pcdhip_buf* x_hat,
+                         pcdhip_buf* z_poly, pcdhip_buf* w, pcdhip_buf* w_rem, pcdhip_buf* za_poly, pcdhip_buf* zb_poly, pcdhip_buf* za_evals,
+                         pcdhip_buf* zb_evals, size_t out_lens[5]) {
+  if (!ctx || !mats || !z || !x_hat || !z_poly || !w_rem || !za_poly || !zb_poly || !out_lens || !(mats->forms & 2)) return PCDHIP_E_ARG;
+  if ((k_w && !blind_w_mont) || (k_a && !blind_a_mont) || (k_b && !blind_b_mont) || k_w >= kMaxLen || k_a >= kMaxLen || k_b >= kMaxLen)
+    return PCDHIP_E_ARG;
+  const int f = mats->field_id;
+  const size_t h_n = mats->domain_h_n, x_n = mats->domain_x_n, w_len = h_n + k_w - x_n;
+  if (!same_field(f, {z, x_hat, z_poly, w, w_rem, za_poly, zb_poly, za_evals, zb_evals})) return PCDHIP_E_ARG;
+  if (!all_distinct({z, x_hat, z_poly, w, w_rem, za_poly, zb_poly, za_evals, zb_evals})) return PCDHIP_E_ARG;
+  if (z->n < mats->num_cols || x_hat->n < x_n || z_poly->n < h_n + k_w || w_rem->n < x_n || za_poly->n < h_n + k_a || zb_poly->n < h_n + k_b)
+    return PCDHIP_E_ARG;
+  if ((w_len && (!w || w->n < w_len)) || (za_evals && za_evals->n < h_n) || (zb_evals && zb_evals->n < h_n)) return PCDHIP_E_ARG;
+  Dom dh, dx;
+  if (pick_domain(f, h_n, &dh) != PCDHIP_OK || pick_domain(f, x_n, &dx) != PCDHIP_OK) return PCDHIP_E_ARG;
+  BIND();
+  const FieldEntry& fe = field_entry(f);
+  TRY(ctx->aux_ws.ensure(AUX_MARLIN_BLIND, std::max<size_t>(k_w + k_a + k_b, 1) * fe.abi_words * 4));
+  // x^: the instance variables (those below num_cols) interpolated on X
+  int rc = transform_abi(ctx, f, dx, z->dptr, std::min<size_t>(x_n, mats->num_cols), x_hat->dptr, x_n, 1);
+  if (rc) return rc;
+  // z_poly: the assignment at pi's places, interpolated on H, blinded
+  TRY(fe.marlin_place(ctx->stream, z->dptr, mats->num_cols, x_n, h_n, z_poly->dptr));
+  rc = transform_abi(ctx, f, dh, z_poly->dptr, h_n, z_poly->dptr, h_n, 1);
+  rc = rc ? rc : add_vanishing_dev(ctx, fe, z_poly->dptr, h_n, blind_w_mont, k_w, h_n, 0);
+  if (rc) return rc;
+  // w = (z_poly - x^) / v_X: x^ is of degree below |X|, so the quotient is z_poly's and the remainder is z_poly's minus x^
+  TRY(ctx->aux_ws.ensure(AUX_MARLIN_WS, 2 * (h_n + k_w) * fe.abi_words * 4));
+  rc = div_vanishing_small_n(ctx, fe, z_poly->dptr, h_n + k_w, x_n, w_len ? w->dptr : nullptr, w_rem->dptr, (uint32_t*)ctx->aux_ws.buf[AUX_MARLIN_WS]);
+  if (rc) return rc;
+  TRY(fe.vec_addsub(ctx->stream, w_rem->dptr, x_hat->dptr, x_n, 1, w_rem->dptr));
+  // z_A, z_B on H (into the caller's vectors, or into the polynomials' own buffers), interpolated, blinded
+  uint32_t* const ev[3] = {za_evals ? za_evals->dptr : za_poly->dptr, zb_evals ? zb_evals->dptr : zb_poly->dptr, nullptr};
+  rc = zm_evals_dev(ctx, mats, z->dptr, ev);
+  rc = rc ? rc : transform_abi(ctx, f, dh, ev[0], h_n, za_poly->dptr, h_n, 1);
+  rc = rc ? rc : add_vanishing_dev(ctx, fe, za_poly->dptr, h_n, blind_a_mont, k_a, h_n, k_w);
+  rc = rc ? rc : transform_abi(ctx, f, dh, ev[1], h_n, zb_poly->dptr, h_n, 1);
+  rc = rc ? rc : add_vanishing_dev(ctx, fe, zb_poly->dptr, h_n, blind_b_mont, k_b, h_n, k_w + k_a);
+  if (rc) return rc;
+  out_lens[0] = x_n; out_lens[1] = h_n + k_w; out_lens[2] = w_len; out_lens[3] = h_n + k_a; out_lens[4] = h_n + k_b;
+  TRY(hipStreamSynchronize(ctx->stream));  // the blinding coefficients are the caller's memory
+  return PCDHIP_OK;
+}
+
+int pcdhip_marlin_sumcheck1(pcdhip_ctx* ctx, const pcdhip_marlin_mats* mats, const uint64_t* eta_mont, const uint64_t* alpha_mont,
+                            const pcdhip_buf* za_poly, size_t len_za, const pcdhip_buf* zb_poly, size_t len_zb, const pcdhip_buf* z_poly,
+                            size_t len_z, const pcdhip_buf* mask, size_t len_mask, size_t domain_d_n, pcdhip_buf* t_poly, pcdhip_buf* h1,
+                            pcdhip_buf* g1, pcdhip_buf* sigma, size_t out_lens[3]) {
+  if (!ctx || !mats || !eta_mont || !alpha_mont || !za_poly || !zb_poly || !z_poly || !t_poly || !sigma || !out_lens || !(mats->forms & 1))
+    return PCDHIP_E_ARG;
+  const int f = mats->field_id;
+  const size_t h_n = mats->domain_h_n;
+  if (!mask) len_mask = 0;
+  if (!same_field(f, {za_poly, zb_poly, z_poly, mask, t_poly, h1, g1, sigma})) return PCDHIP_E_ARG;
+  if (len_za == 0 || len_zb == 0 || len_z == 0 || len_za > za_poly->n || len_zb > zb_poly->n || len_z > z_poly->n || (mask && len_mask > mask->n))
+    return PCDHIP_E_ARG;
+  if (len_za >= kMaxLen || len_zb >= kMaxLen || len_z >= kMaxLen || len_mask >= kMaxLen) return PCDHIP_E_ARG;
+  // outputs apart from each other and from the inputs (the inputs may coincide among themselves)
+  for (const pcdhip_buf* in : {za_poly, zb_poly, z_poly, mask})
+    if (!all_distinct({in, (const pcdhip_buf*)t_poly, (const pcdhip_buf*)h1, (const pcdhip_buf*)g1, (const pcdhip_buf*)sigma})) return PCDHIP_E_ARG;
+  // the longest product r(alpha, .) z_A z_B decides D; q itself may be longer by t z or the mask
+  const size_t prod_len = h_n + len_za + len_zb - 2, q_len = std::max({prod_len, h_n + len_z - 1, len_mask});
+  Dom dh, dd;
+  if (pick_domain(f, h_n, &dh) != PCDHIP_OK) return PCDHIP_E_ARG;
+  if (domain_d_n) {
+    int rc = split_domain(f, domain_d_n, &dd);
+    if (rc) return rc == PCDHIP_E_ARG ? PCDHIP_E_SIZE_UNSUPPORTED : rc;
+    if (domain_d_n < q_len) return PCDHIP_E_ARG;
+  } else if (q_len >= kMaxLen || pick_domain(f, prod_len, &dd) != PCDHIP_OK) return PCDHIP_E_SIZE_UNSUPPORTED;
+  else if (dd.n < q_len) return PCDHIP_E_ARG;
+  const size_t h1_len = q_len - h_n, g1_len = h_n - 1, d_n = dd.n;
+  if (t_poly->n < h_n || sigma->n < 1 || (h1_len && (!h1 || h1->n < h1_len)) || (g1_len && (!g1 || g1->n < g1_len))) return PCDHIP_E_ARG;
+  BIND();
+  const FieldEntry& fe = field_entry(f);
+  const size_t eb = (size_t)fe.abi_words * 4;
+  // one block: r(alpha, .) on H and then its coefficients | the five vectors on D (the first becomes q) | the remainder mod v_H
+  TRY(ctx->aux_ws.ensure(AUX_MARLIN_WS, (2 * h_n + 5 * d_n) * eb));
+  uint32_t* const r_h = (uint32_t*)ctx->aux_ws.buf[AUX_MARLIN_WS];
+  uint32_t* ev[5];
+  for (int k = 0; k < 5; k++) ev[k] = r_h + (h_n + k * d_n) * fe.abi_words;
+  uint32_t* const rem = ev[4] + d_n * fe.abi_words;
+  int rc = lagrange_dev(ctx, f, h_n, alpha_mont, r_h);
+  rc = rc ? rc : t_evals_dev(ctx, mats, eta_mont, r_h, t_poly->dptr);
+  rc = rc ? rc : transform_abi(ctx, f, dh, r_h, h_n, r_h, h_n, 1);
+  rc = rc ? rc : transform_abi(ctx, f, dh, t_poly->dptr, h_n, t_poly->dptr, h_n, 1);
+  // za, zb, r(alpha, .), t, z on D
+  const uint32_t* const src[5] = {za_poly->dptr, zb_poly->dptr, r_h, t_poly->dptr, z_poly->dptr};
+  const size_t src_len[5] = {len_za, len_zb, h_n, h_n, len_z};
+  for (int k = 0; k < 5 && !rc; k++) rc = transform_abi(ctx, f, dd, src[k], src_len[k], ev[k], d_n, 0);
+  if (rc) return rc;
+  TRY(fe.marlin_sumcheck1_q(ctx->stream, (const uint32_t*)eta_mont, ev[0], ev[1], ev[2], ev[3], ev[4], d_n, ev[0]));
+  rc = transform_abi(ctx, f, dd, ev[0], d_n, ev[0], d_n, 1);
+  if (rc) return rc;
+  if (len_mask) TRY(fe.vec_addsub(ctx->stream, ev[0], mask->dptr, len_mask, 0, ev[0]));
+  // q = h_1 v_H + (sigma_1 / |H| + X g_1)
+  TRY(fe.poly_div_vanishing(ctx->stream, ev[0], q_len, h_n, h1_len ? h1->dptr : nullptr, rem));
+  TRY(hipMemcpyAsync(sigma->dptr, rem, eb, hipMemcpyDeviceToDevice, ctx->stream));
+  if (g1_len) TRY(hipMemcpyAsync(g1->dptr, rem + fe.abi_words, g1_len * eb, hipMemcpyDeviceToDevice, ctx->stream));
+  out_lens[0] = h_n; out_lens[1] = h1_len; out_lens[2] = g1_len;
+  return PCDHIP_OK;
 }
 
 }  // extern "C"

@@ -97,6 +97,11 @@ struct pcdhip_marlin_mats {
   uint32_t seg_len = 0;
   void* dev = nullptr;  // one block: the three matrices, then the segment tables
   pcd::MarlinMatsDev view;
+  // K11 (pcdhip_marlin_mats_upload_ex): which forms the handle holds -- bit 0 the transposed matrices above, bit 1 the forward A, B, C
+  // of pcdhip_marlin_zm_evals in a block of their own (null without bit 1)
+  unsigned forms = 1;
+  void* dev_fwd = nullptr;
+  pcd::DevCsr fwd[3];
 };
 struct pcdhip_g16_pk {
   // constraint matrices kept resident by pcdhip_g16_pk_set_r1cs (fixed per circuit, like the key)
@@ -325,6 +330,16 @@ struct FieldEntry {
   // K10 (marlin.hip.h marlin_index_arith): the twelve evaluation vectors on K of an index, one launch.  domain_consts / tw / tw_len of
   // the domain H as for marlin_lagrange (null, null, 1 for |H| = 1)
   hipError_t (*marlin_index_arith)(hipStream_t, const void* domain_consts, const uint32_t* tw, uint32_t tw_len, const MarlinIndexIn& in);
+  // K11 (marlin.hip.h), ABI vectors on the device.  The first sumcheck's q_i = r_i (za_i (eta_A + eta_C zb_i) + eta_B zb_i) - t_i z_i,
+  // one launch; q_out may be one of the inputs
+  hipError_t (*marlin_sumcheck1_q)(hipStream_t, const uint32_t* eta_abi, const uint32_t* za, const uint32_t* zb, const uint32_t* r,
+                                   const uint32_t* t, const uint32_t* z, uint64_t n, uint32_t* q_out);
+  // out[pi(c)] = z[c] for the h_n places of H (x_n divides h_n), variables at and beyond num_cols read as 0; out is not z
+  hipError_t (*marlin_place)(hipStream_t, const uint32_t* z, uint64_t num_cols, uint64_t x_n, uint64_t h_n, uint32_t* out);
+  // out_i = a_i + b_i, or a_i - b_i with sub != 0, for i < n; out may be a or b
+  hipError_t (*vec_addsub)(hipStream_t, const uint32_t* a, const uint32_t* b, uint64_t n, int sub, uint32_t* out);
+  // p += blind (X^n - 1), blind: k ABI coefficients on the device; p holds max(len, n + k) coefficients, those beyond len zeroed
+  hipError_t (*poly_add_vanishing)(hipStream_t, uint32_t* p, const uint32_t* blind, uint64_t k, uint64_t n);
 };
 const FieldEntry& field_entry(int field_id);
 

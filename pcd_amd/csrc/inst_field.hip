@@ -44,6 +44,12 @@ hipError_t PCD_CAT(pcd_marlin_sumcheck_ab_, PCD_FIELD_IDX)(hipStream_t, const ui
                                                            const uint32_t* const val[3], uint64_t n, uint32_t* a_out, uint32_t* b_out);
 hipError_t PCD_CAT(pcd_marlin_index_arith_, PCD_FIELD_IDX)(hipStream_t, const void* domain_consts, const uint32_t* tw, uint32_t tw_len,
                                                            const MarlinIndexIn& in);
+// ... and K11: the first sumcheck's q, the placement of the assignment, a +- b, p += blind (X^n - 1)
+hipError_t PCD_CAT(pcd_marlin_sumcheck1_q_, PCD_FIELD_IDX)(hipStream_t, const uint32_t* eta_abi, const uint32_t* za, const uint32_t* zb,
+                                                           const uint32_t* r, const uint32_t* t, const uint32_t* z, uint64_t n, uint32_t* q_out);
+hipError_t PCD_CAT(pcd_marlin_place_, PCD_FIELD_IDX)(hipStream_t, const uint32_t* z, uint64_t num_cols, uint64_t x_n, uint64_t h_n, uint32_t* out);
+hipError_t PCD_CAT(pcd_marlin_addsub_, PCD_FIELD_IDX)(hipStream_t, const uint32_t* a, const uint32_t* b, uint64_t n, int sub, uint32_t* out);
+hipError_t PCD_CAT(pcd_marlin_add_vanishing_, PCD_FIELD_IDX)(hipStream_t, uint32_t* p, const uint32_t* blind, uint64_t k, uint64_t n);
 
 namespace {
 
@@ -642,7 +648,9 @@ const FieldEntry* PCD_CAT(pcd_field_entry_, PCD_FIELD_IDX)() {
                                mixed_make_tables, mixed_run, mixed_mul_sub_divz, scale_canon, SETUP_CONSTS, setup_scalars, run_batched_entry, spmv3,
                                poly_scratch_words, poly_eval, poly_lincomb_run, vec_mul_run, vec_batch_inverse_run,
                                poly_div_vanishing_run, poly_commit_scalars_run, marlin_lagrange_run, marlin_t_evals_run,
-                               PCD_CAT(pcd_marlin_sumcheck_ab_, PCD_FIELD_IDX), PCD_CAT(pcd_marlin_index_arith_, PCD_FIELD_IDX)};
+                               PCD_CAT(pcd_marlin_sumcheck_ab_, PCD_FIELD_IDX), PCD_CAT(pcd_marlin_index_arith_, PCD_FIELD_IDX),
+                               PCD_CAT(pcd_marlin_sumcheck1_q_, PCD_FIELD_IDX), PCD_CAT(pcd_marlin_place_, PCD_FIELD_IDX),
+                               PCD_CAT(pcd_marlin_addsub_, PCD_FIELD_IDX), PCD_CAT(pcd_marlin_add_vanishing_, PCD_FIELD_IDX)};
   return &e;
 }
 

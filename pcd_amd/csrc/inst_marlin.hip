@@ -1,6 +1,7 @@
 // One object per scalar field (compile with -DPCD_FIELD_IDX=0..3): the K9 kernels whose products are inlined (marlin.hip.h) -- the
-// differences behind r(alpha, .) on H, the rational sumcheck, and the K10 arithmetisation of the index.  A unit of its own so that their 753-bit bodies compile beside the
-// field objects; inst_field.hip puts the two entries into its FieldEntry.
+// differences behind r(alpha, .) on H, the rational sumcheck, the K10 arithmetisation of the index, and K11's first sumcheck with the
+// small kernels of round 1.  A unit of its own so that their 753-bit bodies compile beside the
+// field objects; inst_field.hip puts the entries into its FieldEntry.
 #include "common.h"
 #include <string.h>
 
@@ -71,6 +72,35 @@ hipError_t PCD_CAT(pcd_marlin_index_arith_, PCD_FIELD_IDX)(hipStream_t st, const
   a.w_len = tw ? w.pow_u64(tw_len) : FTP::one();
   FTP::one().to_abi(a.one_abi.w);
   hipLaunchKernelGGL(marlin_index_arith<FTP>, dim3((in.k_n + 255) / 256, 3), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// K11: the first sumcheck's q in one launch (q_out may be one of the inputs), and the three small kernels of round 1 -- the placement
+// of the assignment on H, out = a +- b, p += blind (X^n - 1); all vectors ABI words on the device, eta in ABI words on the host
+hipError_t PCD_CAT(pcd_marlin_sumcheck1_q_, PCD_FIELD_IDX)(hipStream_t st, const uint32_t* eta_abi, const uint32_t* za, const uint32_t* zb,
+                                                           const uint32_t* r, const uint32_t* t, const uint32_t* z, uint64_t n,
+                                                           uint32_t* q_out) {
+  if (n == 0) return hipSuccess;
+  const MarlinSumcheck1Consts<FTP> k = marlin_sumcheck1_consts<FTP>(eta_abi);
+  hipLaunchKernelGGL(marlin_sumcheck1_q<FTP>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, k, za, zb, r, t, z, n, q_out);
+  return hipGetLastError();
+}
+hipError_t PCD_CAT(pcd_marlin_place_, PCD_FIELD_IDX)(hipStream_t st, const uint32_t* z, uint64_t num_cols, uint64_t x_n, uint64_t h_n,
+                                                     uint32_t* out) {
+  if (h_n == 0) return hipSuccess;
+  hipLaunchKernelGGL(marlin_place_assignment<FTP::ABI_WORDS>, dim3((uint32_t)((h_n + 255) / 256)), dim3(256), 0, st, z, num_cols, x_n,
+                     h_n / x_n, h_n, out);
+  return hipGetLastError();
+}
+hipError_t PCD_CAT(pcd_marlin_addsub_, PCD_FIELD_IDX)(hipStream_t st, const uint32_t* a, const uint32_t* b, uint64_t n, int sub, uint32_t* out) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(marlin_vec_addsub<FTP>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a, b, n, sub, out);
+  return hipGetLastError();
+}
+hipError_t PCD_CAT(pcd_marlin_add_vanishing_, PCD_FIELD_IDX)(hipStream_t st, uint32_t* p, const uint32_t* blind, uint64_t k, uint64_t n) {
+  if (k == 0) return hipSuccess;
+  const uint64_t lanes = k <= n ? 2 * k : n + k;
+  hipLaunchKernelGGL(marlin_add_vanishing_multiple<FTP>, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, st, p, blind, k, n);
   return hipGetLastError();
 }
 

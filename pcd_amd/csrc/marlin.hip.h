@@ -193,4 +193,89 @@ __global__ void __launch_bounds__(256) marlin_index_arith(const MarlinIndexArgs<
   (F::unpack32(a.coeff[M] + (size_t)k * AW) * wh).canonical().pack32(val_out);
 }
 
+// ---- K11, round 1 and the first sumcheck.
+// The pointwise core of the first sumcheck's quotient: for i < n
+//   q_i = r_i (za_i (eta_A + eta_C zb_i) + eta_B zb_i) - t_i z_i
+// from five vectors read once as ABI words (the scale R), one store.  Scales: u = eta_C zb + eta_A on R' (eta_C brought to R'^2 / R on
+// the host, eta_A to R'), s = za u + eta_B zb on R (eta_B on R'), d = r s - t z on R^2 / R' -- t and z are both as read, so their
+// product cannot land on R by a constant's scale -- and q = d cin on R, the ABI image.  The five products of the formula are one
+// product and two fused pairs (Fp::dot2: two products under ONE reduction each), the sixth brings d to the scale R: four product
+// sites, six products' multiply-adds, four reductions.  Every load of element i precedes its store and no pointer is declared
+// restrict, so q_out may be any one of the inputs (or several, when those are the same vector).
+template <class F>
+struct MarlinSumcheck1Consts { F eta_a, eta_b, eta_c2; };  // eta_A, eta_B on the scale R', eta_C on R'^2 / R
+template <class F>
+inline MarlinSumcheck1Consts<F> marlin_sumcheck1_consts(const uint32_t* eta_abi) {
+  constexpr int AW = F::ABI_WORDS;
+  F cin;
+  for (int i = 0; i < F::N; i++) cin.v[i] = F::Params::cin(i);
+  MarlinSumcheck1Consts<F> k;
+  k.eta_a = F::from_abi(eta_abi);
+  k.eta_b = F::from_abi(eta_abi + AW);
+  k.eta_c2 = F::from_abi(eta_abi + 2 * AW) * cin;
+  return k;
+}
+// element i of q (host and device, like marlin_sumcheck_element)
+template <class F>
+PCD_HD void marlin_sumcheck1_element(const MarlinSumcheck1Consts<F>& k, const uint32_t* za, const uint32_t* zb, const uint32_t* r,
+                                     const uint32_t* t, const uint32_t* z, uint64_t i, uint32_t* q_out) {
+  constexpr int AW = F::ABI_WORDS;
+  F cin;
+#pragma unroll
+  for (int j = 0; j < F::N; j++) cin.v[j] = F::Params::cin(j);
+  const F b = F::unpack32(zb + i * AW);
+  const F u = k.eta_c2 * b + k.eta_a;
+  const F s = F::dot2(F::unpack32(za + i * AW), u, k.eta_b, b);
+  const F d = F::dot2(F::unpack32(r + i * AW), s, F::unpack32(t + i * AW).neg(), F::unpack32(z + i * AW));
+  (d * cin).canonical().pack32(q_out + i * AW);
+}
+template <class F>
+__global__ void __launch_bounds__(256) marlin_sumcheck1_q(const MarlinSumcheck1Consts<F> k, const uint32_t* za, const uint32_t* zb,
+                                                          const uint32_t* r, const uint32_t* t, const uint32_t* z, uint64_t n,
+                                                          uint32_t* q_out) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) marlin_sumcheck1_element<F>(k, za, zb, r, t, z, i, q_out);
+}
+
+// z on H at reindex_by_subdomain's places, a gather without arithmetic: lane k < h_n finds the variable c with pi(c) = k -- k / period
+// on the subdomain X (k a multiple of period), else x_n + (k - k / period - 1) -- and copies its ABI words; c >= num_cols reads as 0.
+// period == 1 (X = H): every k is on X, out[k] = z[k].
+template <int AW>
+__global__ void __launch_bounds__(256) marlin_place_assignment(const uint32_t* __restrict__ z, uint64_t num_cols, uint64_t x_n,
+                                                               uint64_t period, uint64_t h_n, uint32_t* __restrict__ out) {
+  const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= h_n) return;
+  const uint64_t c = k % period == 0 ? k / period : x_n + (k - k / period - 1);
+  const uint32_t* src = z + c * AW;
+  uint32_t* dst = out + k * AW;
+#pragma unroll
+  for (int i = 0; i < AW; i++) dst[i] = c < num_cols ? src[i] : 0u;
+}
+
+// out_i = a_i + b_i (sub == 0) or a_i - b_i for i < n, ABI words: linear, so the words are summed as read.  out may be a or b.
+template <class F>
+__global__ void __launch_bounds__(256) marlin_vec_addsub(const uint32_t* a, const uint32_t* b, uint64_t n, int sub, uint32_t* out) {
+  constexpr int AW = F::ABI_WORDS;
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const F x = F::unpack32(a + i * AW), y = F::unpack32(b + i * AW);
+  (sub ? x - y : x + y).canonical().pack32(out + i * AW);
+}
+
+// p <- p + blind(X) (X^n - 1) for blind of k coefficients (ABI words, on the device), over the touched coefficients only: lane l owns
+// index l < k (p_l - blind_l) or n + (l - k) (p + blind_(l - k)) when the two windows are apart (k <= n), and index l < n + k when
+// they overlap.  The caller has zeroed p beyond its old length.
+template <class F>
+__global__ void __launch_bounds__(256) marlin_add_vanishing_multiple(uint32_t* p, const uint32_t* __restrict__ blind, uint64_t k, uint64_t n) {
+  constexpr int AW = F::ABI_WORDS;
+  const uint64_t l = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t lanes = k <= n ? 2 * k : n + k;
+  if (l >= lanes) return;
+  const uint64_t idx = (k <= n && l >= k) ? n + (l - k) : l;
+  F acc = F::unpack32(p + idx * AW);
+  if (idx < k) acc = acc - F::unpack32(blind + idx * AW);
+  if (idx >= n && idx - n < k) acc = acc + F::unpack32(blind + (idx - n) * AW);
+  acc.canonical().pack32(p + idx * AW);
+}
+
 }  // namespace pcd

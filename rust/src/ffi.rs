@@ -9,6 +9,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct pcdhip_g16_pk { _p: [u8; 0] }
 #[repr(C)] pub struct pcdhip_pvk { _p: [u8; 0] }
 #[repr(C)] pub struct pcdhip_marlin_index { _p: [u8; 0] }
+#[repr(C)] pub struct pcdhip_marlin_mats { _p: [u8; 0] }
 #[repr(C)] pub struct pcdhip_csr { pub num_rows: u64, pub row_ptr: *const u64, pub col: *const u32, pub coeff: *const u64 }
 #[repr(C)]
 pub struct pcdhip_g16_pk_host {
@@ -113,6 +114,30 @@ extern "C" {
     pub fn pcdhip_fft_general_dev(ctx: *mut pcdhip_ctx, data: *mut pcdhip_buf, n: usize, inverse: c_int, coset: c_int) -> c_int;
     pub fn pcdhip_poly_evals_on_domain(ctx: *mut pcdhip_ctx, p: *const pcdhip_buf, len: usize, domain_n: usize, coset: c_int,
                                        out: *mut pcdhip_buf) -> c_int;
+    // K11: Marlin's round 1 (the assignment on H, z_A / z_B over the forward matrices, w, hiding) and the first sumcheck (q in one
+    // launch, h_1, g_1); forms: bit 0 the transposed matrices of t(X), bit 1 the forward ones
+    pub fn pcdhip_marlin_mats_upload_ex(ctx: *mut pcdhip_ctx, field: c_int, a: *const pcdhip_csr, b: *const pcdhip_csr, c: *const pcdhip_csr,
+                                        num_cols: usize, domain_h_n: usize, domain_x_n: usize, forms: u32,
+                                        out: *mut *mut pcdhip_marlin_mats) -> c_int;
+    pub fn pcdhip_marlin_mats_free(ctx: *mut pcdhip_ctx, mats: *mut pcdhip_marlin_mats);
+    pub fn pcdhip_marlin_zm_evals(ctx: *mut pcdhip_ctx, mats: *const pcdhip_marlin_mats, z: *const pcdhip_buf, za_out: *mut pcdhip_buf,
+                                  zb_out: *mut pcdhip_buf, zc_out: *mut pcdhip_buf) -> c_int;
+    pub fn pcdhip_marlin_place_assignment(ctx: *mut pcdhip_ctx, field: c_int, domain_h_n: usize, domain_x_n: usize, z: *const pcdhip_buf,
+                                          num_cols: usize, out: *mut pcdhip_buf) -> c_int;
+    pub fn pcdhip_poly_add_vanishing_multiple(ctx: *mut pcdhip_ctx, p: *mut pcdhip_buf, len: usize, blind_mont: *const u64, k: usize,
+                                              domain_n: usize, out_len: *mut usize) -> c_int;
+    pub fn pcdhip_marlin_sumcheck1_q(ctx: *mut pcdhip_ctx, eta_mont: *const u64, za: *const pcdhip_buf, zb: *const pcdhip_buf,
+                                     r_alpha: *const pcdhip_buf, t: *const pcdhip_buf, z: *const pcdhip_buf, n: usize,
+                                     q_out: *mut pcdhip_buf) -> c_int;
+    pub fn pcdhip_marlin_round1(ctx: *mut pcdhip_ctx, mats: *const pcdhip_marlin_mats, z: *const pcdhip_buf, blind_w_mont: *const u64, k_w: usize,
+                                blind_a_mont: *const u64, k_a: usize, blind_b_mont: *const u64, k_b: usize, x_hat: *mut pcdhip_buf,
+                                z_poly: *mut pcdhip_buf, w: *mut pcdhip_buf, w_rem: *mut pcdhip_buf, za_poly: *mut pcdhip_buf,
+                                zb_poly: *mut pcdhip_buf, za_evals: *mut pcdhip_buf, zb_evals: *mut pcdhip_buf, out_lens: *mut usize) -> c_int;
+    pub fn pcdhip_marlin_sumcheck1(ctx: *mut pcdhip_ctx, mats: *const pcdhip_marlin_mats, eta_mont: *const u64, alpha_mont: *const u64,
+                                   za_poly: *const pcdhip_buf, len_za: usize, zb_poly: *const pcdhip_buf, len_zb: usize,
+                                   z_poly: *const pcdhip_buf, len_z: usize, mask: *const pcdhip_buf, len_mask: usize, domain_d_n: usize,
+                                   t_poly: *mut pcdhip_buf, h1: *mut pcdhip_buf, g1: *mut pcdhip_buf, sigma: *mut pcdhip_buf,
+                                   out_lens: *mut usize) -> c_int;
 }
 
 /// `PCDHIP_E_*` (include/pcdhip.h)
