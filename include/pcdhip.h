@@ -393,7 +393,10 @@ int pcdhip_multi_pairing(pcdhip_ctx* ctx, int curve_id, const uint64_t* g1_xy, c
  * every entry point that computes pairings (multi_pairing, the Groth16 verifications, process_vk). */
 int pcdhip_pairing_set_mode(pcdhip_ctx* ctx, int mode);
 /* Replaces ark-groth16 `Groth16::verify` (reference call site mod.rs:239):
- * e(A,B) == e(alpha,beta) e(gamma_abc[0] + sum_i x_i gamma_abc[i], gamma) e(C,delta); public inputs canonical, without the leading 1. */
+ * e(A,B) == e(alpha,beta) e(gamma_abc[0] + sum_i x_i gamma_abc[i], gamma) e(C,delta); public inputs canonical, without the leading 1.
+ * Canonical means reduced: every public input is an integer < r.  All four verifications (this one, _batch, _prepared, _batch_rlc)
+ * compare each input with r on the host before anything is enqueued and return PCDHIP_E_ARG when one is >= r -- an error, not a
+ * verdict of 0: x + r would otherwise verify wherever x does, and a caller must be able to tell a bad encoding from a bad proof. */
 int pcdhip_groth16_verify(pcdhip_ctx* ctx, int curve_id, const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* gamma_g2,
                           const uint64_t* delta_g2, const uint64_t* gamma_abc_g1, const uint8_t* gamma_abc_inf, size_t num_inputs,
                           const uint64_t* public_inputs_canonical, const uint64_t* proof, const uint8_t* proof_inf, int* ok);

@@ -40,6 +40,28 @@ int pairing_groups(pcdhip_ctx* ctx, int curve_id, const uint64_t* g1_xy, const u
   return PCDHIP_OK;
 }
 
+// Are all `count` scalars (`into_repr()` images of field `fr`) reduced, i.e. < r?  On the host, before anything is enqueued: the window
+// tables read nwin * 8 bits of a scalar and drop the rest, the MSM refuses only what is wider than r, and either computes x + r as x --
+// so a public input >= r is a second encoding of another statement and is refused as an argument, not answered with a verdict.
+bool scalars_reduced(int fr, const uint64_t* x, size_t count) {
+  bool ok = true;
+  with_host_field(fr, [&](auto f) {
+    typedef typename decltype(f)::type B;
+    typedef typename B::Params P;
+    B m;
+    for (int i = 0; i < B::N; i++) m.v[i] = P::mod(i);
+    uint32_t r[P::N32];
+    m.pack32(r);
+    const uint32_t* w = (const uint32_t*)x;
+    for (size_t s = 0; s < count && ok; s++, w += P::N32) {
+      int i = P::N32 - 1;
+      while (i >= 0 && w[i] == r[i]) i--;
+      ok = i >= 0 && w[i] < r[i];
+    }
+  });
+  return ok;
+}
+
 // acc_i = gamma_abc[0] + sum_j x_ij gamma_abc[j] for k proofs (Jacobian C-ABI image -> affine + flags), through the resident bases
 // acc_z (nullable): when given, non-empty on return iff the accumulations came back in Jacobian form -- (X, Y) in acc_a, Z in acc_z -- which
 // happens with window tables and the wave-per-pairing kernels on (they take Jacobian G1 points: no inversion anywhere in a verification)
@@ -255,6 +277,7 @@ int pcdhip_groth16_verify_prepared(pcdhip_ctx* ctx, const pcdhip_pvk* pvk, size_
   if (!ctx || !pvk || (n_proofs && (!proofs || !ok)) || (pvk->num_inputs > 1 && n_proofs && !public_inputs_canonical) || n_proofs >= (1u << 20))
     return PCDHIP_E_ARG;
   if (n_proofs == 0) return PCDHIP_OK;
+  if (pvk->num_inputs > 1 && !scalars_reduced(kCurveFr[pvk->curve_id], public_inputs_canonical, n_proofs * (pvk->num_inputs - 1))) return PCDHIP_E_ARG;
   BIND();
   const int cid = pvk->curve_id;
   const size_t l1 = (size_t)pcdhip_point_limbs(cid, 1), l2 = (size_t)pcdhip_point_limbs(cid, 2), pl = 2 * l1 + l2, k = n_proofs;
@@ -301,6 +324,7 @@ int pcdhip_groth16_verify_batch_rlc(pcdhip_ctx* ctx, const pcdhip_pvk* pvk, size
   *all_ok = 1;
   if (n_proofs == 0) return PCDHIP_OK;
   for (size_t i = 0; i < n_proofs; i++) if (!(rho[2 * i] | rho[2 * i + 1])) return PCDHIP_E_ARG;  // zero is not a challenge
+  if (pvk->num_inputs > 1 && !scalars_reduced(kCurveFr[pvk->curve_id], public_inputs_canonical, n_proofs * (pvk->num_inputs - 1))) { *all_ok = 0; return PCDHIP_E_ARG; }
   // While the batch's 3k Miller loops find a SIMD each (one wave per pairing: pairing_vm.hip.h) the k verifications side by side take the
   // time of one -- less than the scalings of the combination cost (k = 8: 5.5 against 17 ms on MNT4-298) -- and their answer is the
   // deterministic one.  The random linear combination is for batches that would otherwise queue on the chip.
@@ -395,6 +419,8 @@ int pcdhip_groth16_verify_batch(pcdhip_ctx* ctx, int curve_id, const uint64_t* a
       (num_inputs > 1 && n_proofs && !public_inputs_canonical) || (n_proofs && (!proofs || !ok)) || n_proofs >= (1u << 20))
     return PCDHIP_E_ARG;
   if (n_proofs == 0) return PCDHIP_OK;
+  // (the prepared verification checks this as well; here it saves building the key's tables for a call that is refused)
+  if (num_inputs > 1 && !scalars_reduced(kCurveFr[curve_id], public_inputs_canonical, n_proofs * (num_inputs - 1))) return PCDHIP_E_ARG;
   pcdhip_pvk* pvk = nullptr;
   int rc = pcdhip_process_vk(ctx, curve_id, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, gamma_abc_inf, num_inputs, &pvk);
   if (rc) return rc;

@@ -308,24 +308,52 @@ def test_groth16_roundtrip(co, gpu_ctx, cid, nc):
 
 
 # ---- key generation: fixed-base batches and generate_parameters ------------------------------
-@pytest.mark.parametrize("cid,group,n", [(0, 1, 300), (0, 2, 100), (1, 1, 300), (1, 2, 70), (2, 1, 40), (2, 2, 20), (3, 1, 40), (3, 2, 12)])
+FB_SIZES = [(0, 1, 300), (0, 2, 100), (1, 1, 300), (1, 2, 70), (2, 1, 40), (2, 2, 20), (3, 1, 40), (3, 2, 12)]
+# fb_normalize_kernel shares one inversion among the 8 points of a lane: one lane short of a batch, exactly one, one with a lone point
+# behind it, and a second workgroup that holds a single point (64 lanes x 8 + 1), on the smallest and on the largest group
+FB_SIZES += [(cid, group, n) for cid, group in ((0, 1), (3, 2)) for n in (1, 7, 8, 9, 64 * 8 + 1)]
+
+
+def _fb_zero_slots(n):
+    """where the scalars are zero (the results infinite): slot 0, the middle and the last slot of the first batch of 8, the same of the
+    second batch, the whole third batch, and the last point of all (alone in its batch for n = 9 and n = 64 * 8 + 1); the slots 1 .. 4
+    keep their edge scalars"""
+    z = {0}
+    if n > 5:
+        z |= {5, min(7, n - 1), n - 1}
+    if n >= 16:
+        z |= {11, 15}
+    if n >= 24:
+        z |= set(range(16, 24))
+    return sorted(z)
+
+
+@pytest.mark.parametrize("cid,group,n", FB_SIZES)
 def test_fixed_base_mul_vs_oracle(co, gpu_ctx, cid, group, n):
-    """FixedBaseMSM::multi_scalar_mul + batch normalisation: out[i] = k_i * G, affine, against the oracle's
-    double-and-add; scalars include 0, 1, r - 1 and window-boundary values."""
+    """FixedBaseMSM::multi_scalar_mul + batch normalisation: out[i] = k_i * G, affine -- EVERY output and flag against the oracle's
+    fixed-base batch, a sample of them against its double-and-add as well; scalars include 0, 1, r - 1 and window-boundary values, and
+    zeros (infinite results) at the start, in the middle and at the end of a batch of 8 and through a whole one."""
     fr = co.CURVE_FR[cid]
     sc = co.gen_scalars(fr, n, seed=40 + cid)
-    sc[0] = 0
-    sc[1] = 0; sc[1, 0] = 1
-    sc[2] = 0; sc[2, 0] = 255
-    sc[3] = 0; sc[3, 0] = 256
     one = np.zeros_like(sc[:1]); one[0, 0] = 1
-    sc[4] = co.fp_op(fr, "to_canonical", co.fp_op(fr, "neg", co.fp_op(fr, "from_canonical", one)))[0]   # r - 1
+    edge = [0, 1, 255, 256]
+    for i, v in enumerate(edge[:n]):
+        sc[i] = 0; sc[i, 0] = v
+    if n > 4:
+        sc[4] = co.fp_op(fr, "to_canonical", co.fp_op(fr, "neg", co.fp_op(fr, "from_canonical", one)))[0]   # r - 1
+    zeros = _fb_zero_slots(n)
+    sc[zeros] = 0
+    assert sc[[i for i in range(n) if i not in zeros]].any(axis=1).all()
     base = co.generator(cid, group)
     got, inf = gpu_ctx.fixed_base_mul(cid, group, base, sc)
-    for i in list(range(8)) + list(range(8, n, max(1, n // 24))):
+    want_all, winf_all = co.fixed_base_mul(cid, group, base, sc)
+    assert np.array_equal(inf, winf_all) and list(np.flatnonzero(inf)) == zeros
+    assert not got[inf != 0].any() and np.array_equal(got[inf == 0], want_all[inf == 0])
+    # (the double-and-add takes 0.3 s per point on G2 of a 753-bit curve: two samples behind the first batch at the largest size)
+    for i in list(range(min(8, n))) + (list(range(8, n, max(1, n // 24))) if n <= 300 else [n // 2, n - 2]):
         want, winf = co.to_affine(cid, group, co.scalar_mul(cid, group, base, sc[i])[None])
         assert inf[i] == winf[0] and (inf[i] or np.array_equal(got[i], want[0])), i
-    assert inf[0] == 1 and not got[0].any() and np.array_equal(got[1], base)
+    assert inf[0] == 1 and not got[0].any() and (n < 2 or np.array_equal(got[1], base))
     # an infinity base and an empty batch
     z, zinf = gpu_ctx.fixed_base_mul(cid, group, np.zeros_like(base), sc[:9])
     assert zinf.all() and not z.any()
