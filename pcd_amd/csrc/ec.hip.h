@@ -444,6 +444,59 @@ struct EC {
     return o;
   }
 
+  // ---- full addition of two such accumulators (EFD add-2008-s: 12M + 2S) -- what sums flushed records without turning them into
+  // Jacobian points first (the edge pass and the first reduction level of msm.hip.h).  Same number format on both sides and for the
+  // result, so a sum can be fed back as either operand:
+  //   U1 = X1 ZZ2   U2 = X2 ZZ1   S1 = Y1 ZZZ2   S2 = Y2 ZZZ1   P = U2 - U1   R = S2 - S1   PP = P^2   PPP = P PP   Q = U1 PP
+  //   X3 = R^2 - PPP - 2Q   Y3 = R (Q - X3) - S1 PPP (one fused two-term product)   ZZ3 = ZZ1 ZZ2 PP   ZZZ3 = ZZZ1 ZZZ2 PPP
+  // 10 products, 2 squares and the fused one: 14 against 2 + 2 + 16 for two conversions and the Jacobian add-2007-bl.  An unreduced X
+  // costs nothing: it enters only through U1 / U2, whose product absorbs it.  Bounds (value as a multiple of p | ca cb <= 1024 for a
+  // product | limb products per column < 2^63), for inputs X1, X2 < 16p carried, everything else in [0, 2p):
+  //   U1, U2: 16 * 2 = 32, result < 2p      S1, S2: 2 * 2 = 4, < 2p
+  //   P = U2 - U1 + 4p in (2p, 6p) (carried)   R = S2 - S1 + 4p in (2p, 6p) (carried)   PP, R^2: 6 * 6 = 36   PPP: 6 * 2 = 12   Q: 2 * 2 = 4
+  //   X3 = R^2 - PPP - 2Q + 8p in (2p, 10p) (carried): inside the 16p the format allows, so no reduction is needed anywhere
+  //   t = Q - X3 + 16p in (6p, 16p), limbs in (-2^28, 1.25 * 2^30)   S1' = 4p - S1 in (2p, 4p], limbs in (-2^28, 2^29)
+  //   Y3 = R t + S1' PPP: 6 * 16 + 4 * 2 = 104   ZZ1 ZZ2, ZZZ1 ZZZ2, (ZZ1 ZZ2) PP, (ZZZ1 ZZZ2) PPP: 2 * 2 = 4 each
+  //   columns: carried operands have limbs < 2^28 (the top limb of X < 16p is < 2^22), so every plain product stays below
+  //   11 * 2^56 + 11 * 2^56 (the m p terms) < 2^61; Y3 as in madd_lz: 11 (2^28 * 1.25 * 2^30 + 2^29 * 2^28) + 11 * 2^56 < 2^62
+  // Closed under chaining: X3 < 10p <= 16p and Y3, ZZ3, ZZZ3 in [0, 2p) are again inputs of either side.
+  PCD_HD static AccLz add_lz(const AccLz& p, const AccLz& q) {
+    typedef typename F::Lz L;
+    if (p.inf) return q;
+    if (q.inf) return p;
+    const F U1 = F::lz_mul(p.X, q.ZZ.lz());
+    const F U2 = F::lz_mul(q.X, p.ZZ.lz());
+    const F S1 = F::lz_mul(p.Y.lz(), q.ZZZ.lz());
+    const F S2 = F::lz_mul(q.Y.lz(), p.ZZZ.lz());
+    const L P = F::lz_carry(F::template lz_sub<0>(U2.lz(), U1.lz()));
+    const L R = F::lz_carry(F::template lz_sub<0>(S2.lz(), S1.lz()));
+    const F PP = F::lz_sqr(P);
+    const F RR = F::lz_sqr(R);
+    if (PP.is_zero()) {  // same x: the same point (double it the ordinary way) or opposite points
+      if (!RR.is_zero()) return lz_infinity();
+      return lz_from(dbl(lz_to_jac(p)));
+    }
+    const L pp = PP.lz();
+    const F PPP = F::lz_mul(P, pp);
+    const F Q = F::lz_mul(U1.lz(), pp);
+    AccLz o;
+    o.inf = false;
+    {  // X3 = R^2 - PPP - 2Q + 8p
+      L t;
+#pragma unroll
+      for (int i = 0; i < F::N; i++)
+        t.v[i] = (int32_t)RR.v[i] - (int32_t)PPP.v[i] - (int32_t)(Q.v[i] << 1) + (int32_t)(F::Params::mod4(i) << 1);
+      o.X = F::lz_carry(t);
+    }
+    const L t2 = F::template lz_sub<2>(Q.lz(), o.X);
+    const L s1n = F::template lz_sub<0>(F::zero().lz(), S1.lz());
+    const L ppp = PPP.lz();
+    o.Y = F::lz_dot2(R, t2, s1n, ppp);
+    o.ZZ = F::lz_mul(F::lz_mul(p.ZZ.lz(), q.ZZ.lz()).lz(), pp);
+    o.ZZZ = F::lz_mul(F::lz_mul(p.ZZZ.lz(), q.ZZZ.lz()).lz(), ppp);
+    return o;
+  }
+
   // The same addition with the accumulator held OUTSIDE the register file (ST: four slots of N words per lane -- msm.hip.h keeps them in LDS):
   // every coordinate is fetched when a product needs it and written back as soon as its new value exists, so at most one of the four is in
   // registers at a time.  The point of it: the 298-bit G1 accumulation needs 206 registers with the accumulator resident -- two waves per

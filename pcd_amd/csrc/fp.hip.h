@@ -514,26 +514,30 @@ struct Fp {
 #pragma unroll
     for (int i = 0; i < N; i++) a2[i] = a.v[i] * 2;
     int64_t acc = 0;
+    PCD_LZ_WIDE_DECL
 #pragma unroll
     for (int k = 0; k < N; k++) {
 #pragma unroll
-      for (int i = 0; 2 * i < k; i++) { acc += (int64_t)a2[i] * a.v[k - i]; PCD_KEEP_S(acc); }
-      if ((k & 1) == 0) { acc += (int64_t)a.v[k / 2] * a.v[k / 2]; PCD_KEEP_S(acc); }
+      for (int i = 0; 2 * i < k; i++) { acc += (int64_t)a2[i] * a.v[k - i]; PCD_KEEP_S(acc); PCD_LZ_WIDE_MAC(a2[i], a.v[k - i]) }
+      if ((k & 1) == 0) { acc += (int64_t)a.v[k / 2] * a.v[k / 2]; PCD_KEEP_S(acc); PCD_LZ_WIDE_MAC(a.v[k / 2], a.v[k / 2]) }
 #pragma unroll
-      for (int i = 0; i < k; i++) { acc += (int64_t)m[i] * (int32_t)P::mod(k - i); PCD_KEEP_S(acc); }
+      for (int i = 0; i < k; i++) { acc += (int64_t)m[i] * (int32_t)P::mod(k - i); PCD_KEEP_S(acc); PCD_LZ_WIDE_MAC(m[i], P::mod(k - i)) }
       m[k] = (int32_t)(((uint32_t)acc * P::INV) & MASK);
       acc += (int64_t)m[k] * (int32_t)P::mod(0); PCD_KEEP_S(acc);
+      PCD_LZ_WIDE_MAC(m[k], P::mod(0))
+      PCD_LZ_WIDE_CHECK();
       acc >>= 28;
     }
     Fp r;
 #pragma unroll
     for (int k = N; k < 2 * N - 1; k++) {
 #pragma unroll
-      for (int i = k - N + 1; 2 * i < k; i++) { acc += (int64_t)a2[i] * a.v[k - i]; PCD_KEEP_S(acc); }
-      if ((k & 1) == 0) { acc += (int64_t)a.v[k / 2] * a.v[k / 2]; PCD_KEEP_S(acc); }
+      for (int i = k - N + 1; 2 * i < k; i++) { acc += (int64_t)a2[i] * a.v[k - i]; PCD_KEEP_S(acc); PCD_LZ_WIDE_MAC(a2[i], a.v[k - i]) }
+      if ((k & 1) == 0) { acc += (int64_t)a.v[k / 2] * a.v[k / 2]; PCD_KEEP_S(acc); PCD_LZ_WIDE_MAC(a.v[k / 2], a.v[k / 2]) }
 #pragma unroll
-      for (int i = k - N + 1; i < N; i++) { acc += (int64_t)m[i] * (int32_t)P::mod(k - i); PCD_KEEP_S(acc); }
+      for (int i = k - N + 1; i < N; i++) { acc += (int64_t)m[i] * (int32_t)P::mod(k - i); PCD_KEEP_S(acc); PCD_LZ_WIDE_MAC(m[i], P::mod(k - i)) }
       r.v[k - N] = (uint32_t)acc & MASK;
+      PCD_LZ_WIDE_CHECK();
       acc >>= 28;
     }
     r.v[N - 1] = (uint32_t)acc;

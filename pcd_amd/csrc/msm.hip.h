@@ -14,7 +14,8 @@
 //                    a chunk edge are emitted as "pieces"; lazily reduced XYZZ accumulator for the 298-bit G1 (int-VALU-bound)
 //   3. msm_fixup / msm_big_segments / msm_big_bucket   one item per chunk edge: the pieces of a bucket that crosses edges are summed
 //   4. msm_tail_level / msm_tail_pair  sum_d d*B_d by blocked running sums, then pair levels (two lanes per group operation); the first
-//                    level takes every bucket from where it lies (msm_bucket_at: flushed records become Jacobian points as they are read)
+//                    level takes every bucket from where it lies (msm_bucket_at: flushed records become Jacobian points as they are read;
+//                    the 298-bit G1 sums the records as they are, EC::add_lz, in the edge pass and the first level: "Epilogue in XYZZ")
 //   5. msm_horner    windows combined by c doublings each (not needed with one precomputed copy of the bases per window)
 //
 // Zero digits never enter the sorted list (upstream skips zero scalars); scalars equal to one go, staged per workgroup, to a list
@@ -906,8 +907,37 @@ struct MsmStored<G, true> {
     a.ZZZ = F::load(p + 3 * F::WORDS);
     return EC<G>::lz_to_jac(a);
   }
+  // the record as it is, for EC::add_lz (an identity record carries ZZ = 0 alone: its other words are whatever the slot held and are
+  // never looked at, so all four loads are issued without a branch)
+  PCD_DEV static typename EC<G>::AccLz load_lz(const uint32_t* p) {
+    typename EC<G>::AccLz a;
+#pragma unroll
+    for (int i = 0; i < F::N; i++) a.X.v[i] = (int32_t)p[i];
+    a.Y = F::load(p + F::WORDS);
+    a.ZZ = F::load(p + 2 * F::WORDS);
+    a.ZZZ = F::load(p + 3 * F::WORDS);
+    a.inf = a.ZZ.is_zero();
+    return a;
+  }
+  PCD_DEV static void store_lz(const typename EC<G>::AccLz& a, uint32_t* dst) {
+    if (a.inf) { F::zero().store(dst + 2 * F::WORDS); return; }
+#pragma unroll
+    for (int i = 0; i < F::N; i++) dst[i] = (uint32_t)a.X.v[i];
+    a.Y.store(dst + F::WORDS);
+    a.ZZ.store(dst + 2 * F::WORDS);
+    a.ZZZ.store(dst + 3 * F::WORDS);
+  }
   static constexpr bool SEPARATE = true;  // flushed buckets live in their own array (wider records); the Jacobian array holds what the edge pass summed
 };
+// Epilogue in XYZZ (the groups with the lazily reduced accumulator): the edge pass and the first reduction level sum flushed records as
+// they are (EC::add_lz: 14 products against 2 + 2 + 16 with both operands converted first), and every non-empty bucket but the two
+// msm_merge_ones_kernel works on ends as ONE record in the record array -- flushed whole by the accumulation, or written there by the edge
+// pass / the big-bucket kernel -- so the first level reads it without the chunk rule.  -DPCD_EPILOGUE_LZ=0 selects the former readers.
+#ifndef PCD_EPILOGUE_LZ
+#define PCD_EPILOGUE_LZ 1
+#endif
+template <class G>
+struct MsmEpilogueLz { static constexpr bool value = PCD_EPILOGUE_LZ != 0 && LazyCapable<typename G::F>::value; };
 
 // Waves per SIMD the register allocation of the accumulate kernel aims at: 2 for the 298-bit G1 (194 registers, no spills);
 // 1 wherever the working set does not fit 256 registers -- the extension fields and everything 753-bit -- so that it lives in
@@ -1361,10 +1391,11 @@ __global__ void __launch_bounds__(64) msm_merge_ones_kernel(uint32_t* __restrict
 // each.  Whole buckets -- their run inside one chunk -- stay where msm_accumulate flushed them and empty ones are written by nobody:
 // the first reduction level takes every bucket from where it lies (msm_bucket_at).  The two buckets msm_merge_ones_kernel works on in
 // place, (window 0, digit 1) and the pseudo bucket, are always materialised in the Jacobian array: items 0 and 1.
+// (Epilogue in XYZZ, MsmEpilogueLz: the sum of a run's pieces is a record in the bucket's own slot of the record array instead.)
 template <class G>
 __global__ void __launch_bounds__(64) msm_fixup_kernel(const uint32_t* __restrict__ off, uint32_t nkeys, const MsmChunkRule rule,
                                                        const uint32_t* __restrict__ piece_first, const uint32_t* __restrict__ piece_last,
-                                                       const uint32_t* __restrict__ acc_buckets /* what msm_accumulate flushed whole buckets into */,
+                                                       uint32_t* acc_buckets /* what msm_accumulate flushed whole buckets into; XYZZ epilogue: the sums go there too */,
                                                        uint32_t* __restrict__ buckets, uint32_t big_limit, uint32_t* __restrict__ big_count,
                                                        uint32_t* __restrict__ big_list /* (key, first segment, #segments) */, uint32_t big_cap,
                                                        uint32_t* __restrict__ seg_list /* (t_lo, t_hi, t_last) */, uint32_t seg_len) {
@@ -1403,10 +1434,21 @@ __global__ void __launch_bounds__(64) msm_fixup_kernel(const uint32_t* __restric
     }
     return;
   }
-  Jac<F> acc = MsmStored<GA>::load(piece_last + (size_t)t0 * RW);
-  for (uint32_t u = t0 + 1; u < t1; u++) acc = E::add(acc, MsmStored<GA>::load(piece_last + (size_t)u * RW));
-  acc = E::add(acc, MsmStored<GA>::load(piece_first + (size_t)t1 * RW));
-  acc.store(buckets + (size_t)key * Jac<F>::WORDS);
+  if constexpr (MsmEpilogueLz<GA>::value) {
+    // the pieces are summed as the records they are; the sum goes, as a record, to the bucket's slot of the record array (the accumulation
+    // writes that slot for whole buckets only) -- except for the two buckets msm_merge_ones_kernel expects in the Jacobian array
+    typedef MsmStored<GA> S;
+    typename E::AccLz acc = S::load_lz(piece_last + (size_t)t0 * RW);
+    for (uint32_t u = t0 + 1; u < t1; u++) acc = E::add_lz(acc, S::load_lz(piece_last + (size_t)u * RW));
+    acc = E::add_lz(acc, S::load_lz(piece_first + (size_t)t1 * RW));
+    if (key == 1 || key == nkeys - 1) E::lz_to_jac(acc).store(buckets + (size_t)key * Jac<F>::WORDS);
+    else S::store_lz(acc, acc_buckets + (size_t)key * RW);
+  } else {
+    Jac<F> acc = MsmStored<GA>::load(piece_last + (size_t)t0 * RW);
+    for (uint32_t u = t0 + 1; u < t1; u++) acc = E::add(acc, MsmStored<GA>::load(piece_last + (size_t)u * RW));
+    acc = E::add(acc, MsmStored<GA>::load(piece_first + (size_t)t1 * RW));
+    acc.store(buckets + (size_t)key * Jac<F>::WORDS);
+  }
 }
 
 // Items of the bucket-reduction levels.  Prime-field groups spend TWO lanes on every item (EC2: 8 product slots per addition
@@ -1445,7 +1487,8 @@ struct MsmPairOps<G, true, Q> {
 // The items of a workgroup sum strided pieces, then a tree through global scratch -- latency-bound chains of additions, so with the
 // item / operation choice of the reduction levels (two lanes per addition for the prime-field groups).
 template <class G>
-PCD_DEV void msm_wave_tree(Jac<typename MsmPairOps<G>::GA::F> acc, uint32_t* my /* PER_WAVE points of scratch */, uint32_t* dst) {
+PCD_DEV void msm_wave_tree(Jac<typename MsmPairOps<G>::GA::F> acc, uint32_t* my /* PER_WAVE points of scratch */, uint32_t* dst,
+                           uint32_t* dst_record = nullptr /* XYZZ epilogue: the result as a record here instead of a Jacobian point at dst */) {
   typedef MsmPairItems<G> IT;
   typedef MsmPairOps<G> O;
   typedef typename O::GA::F F;
@@ -1462,7 +1505,14 @@ PCD_DEV void msm_wave_tree(Jac<typename MsmPairOps<G>::GA::F> acc, uint32_t* my 
     }
     __syncthreads();
   }
-  if (live && it == 0 && IT::writer()) acc.store(dst);
+  if (live && it == 0 && IT::writer()) {
+    if constexpr (MsmEpilogueLz<typename O::GA>::value) {
+      if (dst_record) MsmStored<typename O::GA>::store_lz(EC<typename O::GA>::lz_from(acc), dst_record);
+      else acc.store(dst);
+    } else {
+      acc.store(dst);
+    }
+  }
   __syncthreads();
 }
 template <class G>
@@ -1490,7 +1540,9 @@ __global__ void __launch_bounds__(64) msm_big_segments_kernel(const uint32_t* __
 template <class G>
 __global__ void __launch_bounds__(64) msm_big_bucket_kernel(const uint32_t* __restrict__ big_list, const uint32_t* __restrict__ big_count,
                                                             const uint32_t* __restrict__ partial, uint32_t* __restrict__ buckets,
-                                                            uint32_t* __restrict__ scratch) {
+                                                            uint32_t* __restrict__ scratch,
+                                                            uint32_t* acc_buckets /* XYZZ epilogue: where the sums go, as records */,
+                                                            uint32_t nkeys) {
   typedef MsmPairItems<G> IT;
   typedef MsmPairOps<G> O;
   typedef typename O::GA GA;
@@ -1503,7 +1555,12 @@ __global__ void __launch_bounds__(64) msm_big_bucket_kernel(const uint32_t* __re
     Jac<F> acc = Jac<F>::infinity();
     if (!IT::idle())
       for (uint32_t u = IT::local(); u < ns; u += PW) acc = O::add(acc, Jac<F>::load(partial + (size_t)(s0 + u) * Jac<F>::WORDS));
-    msm_wave_tree<G>(acc, my, buckets + (size_t)key * Jac<F>::WORDS);
+    // (the big segments and this sum stay Jacobian inside -- a few waves; only the result takes the form its reader expects: a record, or
+    //  for the two buckets of msm_merge_ones_kernel the Jacobian point)
+    uint32_t* rec = nullptr;
+    if constexpr (MsmEpilogueLz<GA>::value)
+      if (key != 1 && key != nkeys - 1) rec = acc_buckets + (size_t)key * MsmStored<GA>::WORDS;
+    msm_wave_tree<G>(acc, my, buckets + (size_t)key * Jac<F>::WORDS, rec);
   }
 }
 
@@ -1517,21 +1574,38 @@ __global__ void __launch_bounds__(64) msm_big_bucket_kernel(const uint32_t* __re
 // Jacobian array or writes identities for empty ones.
 struct MsmBucketSrc {
   const uint32_t* off;          // run of bucket `key`: [off[key], off[key + 1])
-  const uint32_t* acc_buckets;  // flushed records of whole buckets (MsmStored; the Jacobian array itself where the flush is Jacobian)
+  const uint32_t* acc_buckets;  // flushed records of whole buckets (MsmStored; the Jacobian array itself where the flush is Jacobian);
+                                // epilogue in XYZZ: one record for every non-empty bucket but bucket 1
   const uint32_t* buckets;      // Jacobian array: buckets summed by the edge pass or the big-bucket kernels, and bucket 1
   uint32_t nkeys;
-  MsmChunkRule rule;
+  MsmChunkRule rule;            // (not looked at by the XYZZ epilogue's readers)
 };
 template <class GA>
 PCD_DEV Jac<typename GA::F> msm_bucket_at(const MsmBucketSrc& bs, uint32_t chunk, uint32_t key) {
   typedef typename GA::F F;
-  if (key != 1) {  // (bucket 1 is always materialised: msm_merge_ones_kernel adds the pseudo bucket to it in place)
-    const uint32_t lo = bs.off[key], hi = bs.off[key + 1];
-    if (hi == lo) return Jac<F>::infinity();
-    if (hi - (lo / chunk) * chunk <= chunk)  // the run ends inside the chunk it starts in (one division)
-      return MsmStored<GA>::load(bs.acc_buckets + (size_t)key * MsmStored<GA>::WORDS);
+  if constexpr (MsmEpilogueLz<GA>::value) {  // every non-empty bucket but bucket 1 is one record of the record array: no chunk rule
+    if (key == 1) return Jac<F>::load(bs.buckets + (size_t)key * Jac<F>::WORDS);
+    if (bs.off[key + 1] == bs.off[key]) return Jac<F>::infinity();
+    return MsmStored<GA>::load(bs.acc_buckets + (size_t)key * MsmStored<GA>::WORDS);
+  } else {
+    if (key != 1) {  // (bucket 1 is always materialised: msm_merge_ones_kernel adds the pseudo bucket to it in place)
+      const uint32_t lo = bs.off[key], hi = bs.off[key + 1];
+      if (hi == lo) return Jac<F>::infinity();
+      if (hi - (lo / chunk) * chunk <= chunk)  // the run ends inside the chunk it starts in (one division)
+        return MsmStored<GA>::load(bs.acc_buckets + (size_t)key * MsmStored<GA>::WORDS);
+    }
+    return Jac<F>::load(bs.buckets + (size_t)key * Jac<F>::WORDS);
   }
-  return Jac<F>::load(bs.buckets + (size_t)key * Jac<F>::WORDS);
+}
+// the same bucket as the record it is (XYZZ epilogue, for EC::add_lz): an empty run is the identity, bucket 1 comes from the Jacobian
+// array, everything else is a plain record load
+template <class GA>
+PCD_DEV typename EC<GA>::AccLz msm_bucket_lz(const MsmBucketSrc& bs, uint32_t key) {
+  typedef typename GA::F F;
+  if (key == 1) return EC<GA>::lz_from(Jac<F>::load(bs.buckets + (size_t)key * Jac<F>::WORDS));
+  typename EC<GA>::AccLz a = MsmStored<GA>::load_lz(bs.acc_buckets + (size_t)key * MsmStored<GA>::WORDS);
+  a.inf = a.inf || bs.off[key + 1] == bs.off[key];  // (nobody writes the slot of an empty bucket)
+  return a;
 }
 // (msm_tail_level_kernel is only ever the first level -- blocks of 8 over a large bucket array: A is the bucket array, window w's digit
 //  d at key w * strideA_in + d, and there is no C yet)
@@ -1551,13 +1625,28 @@ __global__ void __launch_bounds__(64) msm_tail_level_kernel(const MsmBucketSrc b
   uint32_t tid = IT::item();
   uint32_t w = blockIdx.y;
   if (tid < JA) {
-    const uint32_t chunk = bs.rule.eval(bs.off, bs.nkeys);
     const uint32_t key1 = w * (uint32_t)strideA_in + 1;  // digit 1 of window w
     Jac<F> run = Jac<F>::infinity(), acc = Jac<F>::infinity();
-    for (int tt = (int)K - 1; tt >= 0; tt--) {
-      uint32_t i = tid * K + tt;
-      if (i < mA) run = O::add(run, msm_bucket_at<GA>(bs, chunk, key1 + i));
-      acc = O::add(acc, run);
+    if constexpr (MsmEpilogueLz<GA>::value && !IT::TWO) {
+      // one lane per item: the running sums stay XYZZ records through the block (EC::add_lz on the buckets as they lie) and become
+      // Jacobian points once, for the doublings and for the pair levels behind this one
+      typedef EC<GA> E;
+      typename E::AccLz run_lz = E::lz_infinity(), acc_lz = E::lz_infinity();
+      for (int tt = (int)K - 1; tt >= 0; tt--) {
+        uint32_t i = tid * K + tt;
+        if (i < mA) run_lz = E::add_lz(run_lz, msm_bucket_lz<GA>(bs, key1 + i));
+        acc_lz = E::add_lz(acc_lz, run_lz);
+      }
+      run = E::lz_to_jac(run_lz);
+      acc = E::lz_to_jac(acc_lz);
+    } else {
+      uint32_t chunk = 0;
+      if constexpr (!MsmEpilogueLz<GA>::value) chunk = bs.rule.eval(bs.off, bs.nkeys);
+      for (int tt = (int)K - 1; tt >= 0; tt--) {
+        uint32_t i = tid * K + tt;
+        if (i < mA) run = O::add(run, msm_bucket_at<GA>(bs, chunk, key1 + i));
+        acc = O::add(acc, run);
+      }
     }
     if (IT::writer()) acc.store(C_out + (w * strideC_out + JC + tid) * PW);
     if (tid >= 1) {
@@ -1596,7 +1685,7 @@ PCD_DEV void msm_tail_pair_item(int role, uint32_t j, uint32_t w, const uint32_t
   if (role < 2) {
     if (j >= JA) return;
     uint32_t chunk = 0;
-    if constexpr (FIRST) chunk = bs->rule.eval(bs->off, bs->nkeys);
+    if constexpr (FIRST && !MsmEpilogueLz<GA>::value) chunk = bs->rule.eval(bs->off, bs->nkeys);
     auto a_at = [&](uint32_t i) {
       if constexpr (FIRST) return msm_bucket_at<GA>(*bs, chunk, w * (uint32_t)strideA_in + 1 + i);
       else return Jac<F>::load(A_in + (w * strideA_in + i) * PW);
@@ -2147,7 +2236,7 @@ hipError_t msm_run(MsmWorkspace& ws, hipStream_t st, const MsmBasesView& bv, con
     hipLaunchKernelGGL((msm_big_segments_kernel<G>), dim3(big_grid), dim3(64), 0, st, seg_list, big_count, pfirst, plast, big_partial,
                        (uint32_t*)ws.buf[WS_BIGSCR]);
     hipLaunchKernelGGL((msm_big_bucket_kernel<G>), dim3(std::min<uint32_t>(big_cap, 2048)), dim3(64), 0, st, big, big_count, big_partial,
-                       buckets, (uint32_t*)ws.buf[WS_BIGSCR]);
+                       buckets, (uint32_t*)ws.buf[WS_BIGSCR], acc_buckets, tkeys);
   }
   hipLaunchKernelGGL((msm_merge_ones_kernel<G>), dim3(1), dim3(64), 0, st, buckets, ones_key);
   PCD_HIP_TRY(mark(5));
