@@ -753,6 +753,50 @@ int pcdhip_marlin_sumcheck1(pcdhip_ctx* ctx, const pcdhip_marlin_mats* mats, con
                             size_t domain_d_n /* 0: rule */, pcdhip_buf* t_poly, pcdhip_buf* h1, pcdhip_buf* g1, pcdhip_buf* sigma,
                             size_t out_lens[3]);
 
+/* ---- K12 Marlin's second sumcheck: f, g_2 and h_2 -----------------------------------------------------------------------------------
+ * The last prover step of ark-marlin's round 3, on the conventions of K9 - K11: device vectors of ABI Montgomery elements of ONE scalar
+ * field, the context's own stream and workspaces, device 0 of a multi-device context, host field elements as ABI Montgomery limbs,
+ * PCDHIP_E_ARG for bad arguments, no CPU fallback.  Both calls only QUEUE their launches.  ark-marlin is not vendored: the calls are
+ * specified by the formulas written here, and what is said about upstream -- the order of its steps, the rule for |B| -- is RESTATED
+ * FROM MEMORY.
+ *
+ * pcdhip_marlin_sumcheck2_q, the pointwise core: q_i = a_i - b_i f_i for i < n, with a and b EXACTLY those of
+ * pcdhip_marlin_sumcheck_ab (both forms of d_M, the same rule for a NULL row_col), in ONE launch, one lane per element: the thirteen
+ * vectors are read once as ABI words, there is one store, and a and b never reach memory.  Argument rules of
+ * pcdhip_marlin_sumcheck_ab; f and q_out hold at least n elements of the same field.  Aliasing: every load of element i precedes its
+ * store, so q_out may be f (in place); q_out on any of the twelve index vectors is PCDHIP_E_ARG.  n == 0 succeeds without a launch. */
+int pcdhip_marlin_sumcheck2_q(pcdhip_ctx* ctx, const uint64_t* alpha_mont, const uint64_t* beta_mont, const uint64_t* coeff_mont /* 3 */,
+                              const pcdhip_buf* const row[3], const pcdhip_buf* const col[3],
+                              const pcdhip_buf* const row_col[3] /* array or entries nullable */, const pcdhip_buf* const val[3],
+                              const pcdhip_buf* f, size_t n, pcdhip_buf* q_out);
+/* The second sumcheck whole, from an index that kept its evaluations on K and on B (keep bits 1 and 2; PCDHIP_E_ARG otherwise).
+ * coeff_mont = c_A, c_B, c_C is the caller's: eta_M v_H(alpha) v_H(beta) in the prover.  With v_K = X^|K| - 1:
+ *   f on K   = pcdhip_marlin_sumcheck_f over the index's evaluations on K (row_col as the index holds it)
+ *   f_poly   = the interpolation of f on K                                                     |K| coefficients   (nullable)
+ *   f_poly   = sigma + X g_2:   sigma = f_poly's constant term = sigma_2 / |K| = (sum_K f) / |K|   1 element
+ *                               g_2   = f_poly shifted down by one                                 |K| - 1 coefficients
+ *   a, b     = the polynomials of degree <= 3 |K| - 3 whose evaluations on B pcdhip_marlin_sumcheck_ab gives over the index's vectors on
+ *              B: there row_col is the interpolated polynomial, so a and b are the formulas of pcdhip_marlin_sumcheck_ab over the
+ *              POLYNOMIALS row, col, row_col, val
+ *   a - b f_poly = h_2 v_K + remainder:   h_2 3 |K| - 3 coefficients, NOT trimmed;   remainder |K| coefficients
+ * The remainder is ZERO by construction whenever no d_M vanishes on K (a = b f there); it is written to h2_rem when that is given, so
+ * that the caller can see it.  out_lens[0] = |K| - 1, out_lens[1] = 3 |K| - 3, out_lens[2] = the route taken; all three are known on
+ * the host before anything runs.  The outputs are distinct buffers that hold their lengths (g2 and h2 may be NULL for |K| = 1); nothing
+ * is written when the call refuses.
+ * Routes.  deg(a - b f_poly) = 4 |K| - 4, and upstream forms b f_poly as a polynomial product rather than pointwise on B:
+ *   route 1  pointwise on B, needs |B| >= 4 |K| - 3: f_poly zero-padded onto B, pcdhip_marlin_sumcheck2_q there in place over the
+ *            index's vectors, the inverse transform on B, the division by v_K.  Workspace: ONE vector of |B| elements (and 2 |K|)
+ *            beyond the transform's own.
+ *   route 2  upstream's order, needs |B| >= 3 |K| - 2: pcdhip_marlin_sumcheck_ab on B, two inverse transforms on B, b_poly f_poly by
+ *            the steps of pcdhip_poly_mul over pcdhip_domain_size(field, 4 |K| - 3) elements (PCDHIP_E_SIZE_UNSUPPORTED when there is
+ *            none), the subtraction, the division.  Workspace: two vectors of max(|B|, 4 |K| - 3) and a third transform vector.
+ *   route 0  picks 1 when |B| allows it, else 2.  A forced route whose condition fails is PCDHIP_E_ARG.
+ * K10's rule |B| = pcdhip_domain_size(field, 3 |K| - 3) gives 4 |K| for a radix-2 B and about 3.06 |K| for a mixed-radix one, hence
+ * both.  K and B may be mixed-radix: every transform is the library's general one.  Both routes give the same h_2, bit for bit. */
+int pcdhip_marlin_sumcheck2(pcdhip_ctx* ctx, const pcdhip_marlin_index* index, const uint64_t* alpha_mont, const uint64_t* beta_mont,
+                            const uint64_t* coeff_mont /* 3 */, int route /* 0 auto, 1, 2 */, pcdhip_buf* f_poly /* nullable */,
+                            pcdhip_buf* g2, pcdhip_buf* sigma, pcdhip_buf* h2, pcdhip_buf* h2_rem /* nullable */, size_t out_lens[3]);
+
 /* ---- timing helpers (HIP events on the context's stream, for bench.py) ------------------------- */
 int pcdhip_timer_start(pcdhip_ctx* ctx);
 int pcdhip_timer_stop(pcdhip_ctx* ctx, float* out_ms);

@@ -83,6 +83,7 @@ EXPORTS = [
     "pcdhip_fft_general_dev", "pcdhip_poly_evals_on_domain",
     "pcdhip_marlin_mats_upload_ex", "pcdhip_marlin_zm_evals", "pcdhip_marlin_place_assignment", "pcdhip_poly_add_vanishing_multiple",
     "pcdhip_marlin_sumcheck1_q", "pcdhip_marlin_round1", "pcdhip_marlin_sumcheck1",
+    "pcdhip_marlin_sumcheck2_q", "pcdhip_marlin_sumcheck2",
 ]
 
 
@@ -133,6 +134,8 @@ def lib():
         _LIB.pcdhip_marlin_sumcheck1_q.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp]
         _LIB.pcdhip_marlin_round1.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, szp]
         _LIB.pcdhip_marlin_sumcheck1.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, sz, vp, vp, vp, vp, szp]
+        _LIB.pcdhip_marlin_sumcheck2_q.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        _LIB.pcdhip_marlin_sumcheck2.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, szp]
     return _LIB
 
 
@@ -877,6 +880,36 @@ class Context:
             self._ctx, mats._h, _p(eta), _p(_u64(alpha_mont)), za_poly._h, len_za, zb_poly._h, len_zb, z_poly._h, len_z,
             mask._h if mask is not None else None, len_mask, int(domain_d_n), hd("t_poly"), hd("h1"), hd("g1"), hd("sigma"), lens))
         out["lens"] = [int(v) for v in lens]
+        return out
+
+    # ---- K12: the second sumcheck
+    def marlin_sumcheck2_q(self, alpha_mont, beta_mont, coeff_mont, row, col, row_col, val, f, n=None, out=None):
+        """q_i = a_i - b_i f_i for i < n, a and b those of marlin_sumcheck_ab (never stored) -> out (allocated when not passed; may be f)"""
+        n = min(x.n for x in list(row) + list(col) + list(val) + [f]) if n is None else int(n)
+        fld = row[0].field
+        own = [] if out is not None else [self.buf_alloc(fld, n)]
+        out = out if out is not None else own[0]
+        cf = _u64(coeff_mont).reshape(3, FIELD_LIMBS[fld])
+        self._call_into(own, lambda: lib().pcdhip_marlin_sumcheck2_q(self._ctx, _p(_u64(alpha_mont)), _p(_u64(beta_mont)), _p(cf), self._three(row),
+                                                                     self._three(col), self._three(row_col), self._three(val), f._h, n, out._h))
+        return out
+
+    def marlin_sumcheck2(self, index, alpha_mont, beta_mont, coeff_mont, route=0, want_f_poly=True, want_rem=True):
+        """the second sumcheck over an index that kept its evaluations on K and on B -> dict of DeviceBufs f_poly (None without
+        want_f_poly), g2 and h2 (None when empty), sigma (one element), h2_rem (None without want_rem), "lens": the lengths of g2 and
+        h2, and "route": the route taken (1 pointwise on B, 2 by the polynomial product)"""
+        fld = index.field
+        k_n = index.info()["domain_k_n"]
+        sizes = {"f_poly": k_n if want_f_poly else 0, "g2": k_n - 1, "sigma": 1, "h2": 3 * k_n - 3, "h2_rem": k_n if want_rem else 0}
+        out = {name: (self.buf_alloc(fld, n) if n else None) for name, n in sizes.items()}
+        hd = lambda name: out[name]._h if out[name] is not None else None
+        lens = (C.c_size_t * 3)()
+        cf = _u64(coeff_mont).reshape(3, FIELD_LIMBS[fld])
+        self._call_into([b for b in out.values() if b is not None], lambda: lib().pcdhip_marlin_sumcheck2(
+            self._ctx, index._h, _p(_u64(alpha_mont)), _p(_u64(beta_mont)), _p(cf), int(route), hd("f_poly"), hd("g2"), hd("sigma"), hd("h2"),
+            hd("h2_rem"), lens))
+        out["lens"] = [int(lens[0]), int(lens[1])]
+        out["route"] = int(lens[2])
         return out
 
     def fft_general_dev(self, data, n=None, inverse=False, coset=False):

@@ -3,7 +3,8 @@
 // Every call queues its launches on the context's stream and returns: nothing here waits for the device except the upload of the matrices.
 // K10, the index on device (the arithmetisation onto K, the coefficients, the evaluations on B, the twelve commitments), follows below;
 // pcdhip_marlin_index_build waits for its own uploads and for the end of its work.  K11 at the end: round 1 (the assignment on H, z_A and
-// z_B over the forward matrices, w) and the first sumcheck (q in one launch, h_1 and g_1).
+// z_B over the forward matrices, w) and the first sumcheck (q in one launch, h_1 and g_1).  K12 behind it: the second sumcheck (q = a - b f in
+// one launch; f, g_2 and h_2 from an index in one call).
 #include <stdlib.h>
 
 #include "capi_internal.h"
@@ -12,7 +13,8 @@ using namespace pcd;
 
 namespace {
 // (AUX_MARLIN_WS: the vectors of a K11 driver in one block; AUX_MARLIN_BLIND: the blinding coefficients of a call, staged from the host)
-enum { AUX_MARLIN_PART = AUX_FB_OUT + 5, AUX_MARLIN_A, AUX_MARLIN_B, AUX_MARLIN_WS, AUX_MARLIN_BLIND };
+// (AUX_MARLIN_MUL_B: route 2 of the K12 driver, the second operand of its polynomial product over the product's domain)
+enum { AUX_MARLIN_PART = AUX_FB_OUT + 5, AUX_MARLIN_A, AUX_MARLIN_B, AUX_MARLIN_WS, AUX_MARLIN_BLIND, AUX_MARLIN_MUL_B };
 const size_t kMaxLen = (size_t)1 << 31;
 
 bool is_domain_size(int field_id, size_t n) { return n != 0 && n < kMaxLen && pcdhip_domain_size(field_id, n) == n; }
@@ -698,6 +700,119 @@ int pcdhip_marlin_sumcheck1(pcdhip_ctx* ctx, const pcdhip_marlin_mats* mats, con
   TRY(hipMemcpyAsync(sigma->dptr, rem, eb, hipMemcpyDeviceToDevice, ctx->stream));
   if (g1_len) TRY(hipMemcpyAsync(g1->dptr, rem + fe.abi_words, g1_len * eb, hipMemcpyDeviceToDevice, ctx->stream));
   out_lens[0] = h_n; out_lens[1] = h1_len; out_lens[2] = g1_len;
+  return PCDHIP_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ K12: the second sumcheck
+extern "C" {
+
+int pcdhip_marlin_sumcheck2_q(pcdhip_ctx* ctx, const uint64_t* alpha_mont, const uint64_t* beta_mont, const uint64_t* coeff_mont,
+                              const pcdhip_buf* const row[3], const pcdhip_buf* const col[3], const pcdhip_buf* const row_col[3],
+                              const pcdhip_buf* const val[3], const pcdhip_buf* f, size_t n, pcdhip_buf* q_out) {
+  if (!ctx || !f || !q_out) return PCDHIP_E_ARG;
+  SumcheckArgs a;
+  int rc = sumcheck_args(alpha_mont, beta_mont, coeff_mont, row, col, row_col, val, n, &a);
+  if (rc) return rc;
+  if (f->field_id != a.field_id || q_out->field_id != a.field_id || n > f->n || n > q_out->n || is_input(a, q_out->dptr)) return PCDHIP_E_ARG;
+  if (n == 0) return PCDHIP_OK;
+  BIND();
+  TRY(field_entry(a.field_id).marlin_sumcheck2_q(ctx->stream, (const uint32_t*)alpha_mont, (const uint32_t*)beta_mont, (const uint32_t*)coeff_mont,
+                                                 a.row, a.col, a.rc, a.val, f->dptr, n, q_out->dptr));
+  return PCDHIP_OK;
+}
+
+int pcdhip_marlin_sumcheck2(pcdhip_ctx* ctx, const pcdhip_marlin_index* index, const uint64_t* alpha_mont, const uint64_t* beta_mont,
+                            const uint64_t* coeff_mont, int route, pcdhip_buf* f_poly, pcdhip_buf* g2, pcdhip_buf* sigma, pcdhip_buf* h2,
+                            pcdhip_buf* h2_rem, size_t out_lens[3]) {
+  if (!ctx || !index || !alpha_mont || !beta_mont || !coeff_mont || !sigma || !out_lens || route < 0 || route > 2) return PCDHIP_E_ARG;
+  if (!index->block[1] || !index->block[2]) return PCDHIP_E_ARG;
+  const int f = index->field_id;
+  const size_t k_n = index->domain_k_n, b_n = index->domain_b_n;
+  const size_t g2_len = k_n - 1, h2_len = 3 * k_n - 3, q_len = 4 * k_n - 3;
+  if (q_len >= kMaxLen) return PCDHIP_E_SIZE_UNSUPPORTED;
+  // route 1 multiplies b by f on B, where a - b f (4 |K| - 3 coefficients) must fit; route 2 only interpolates a and b there
+  const bool fits1 = b_n >= q_len, fits2 = b_n >= 3 * k_n - 2;
+  if (route == 0) route = fits1 ? 1 : 2;
+  if ((route == 1 && !fits1) || (route == 2 && !fits2)) return PCDHIP_E_ARG;
+  if (!same_field(f, {f_poly, g2, sigma, h2, h2_rem}) || !all_distinct({f_poly, g2, sigma, h2, h2_rem})) return PCDHIP_E_ARG;
+  if (sigma->n < 1 || (f_poly && f_poly->n < k_n) || (h2_rem && h2_rem->n < k_n) || (g2_len && (!g2 || g2->n < g2_len)) ||
+      (h2_len && (!h2 || h2->n < h2_len)))
+    return PCDHIP_E_ARG;
+  Dom dk, db, dm;
+  if (split_domain(f, k_n, &dk) != PCDHIP_OK || split_domain(f, b_n, &db) != PCDHIP_OK) return PCDHIP_E_ARG;
+  if (route == 2 && pick_domain(f, q_len, &dm) != PCDHIP_OK) return PCDHIP_E_SIZE_UNSUPPORTED;
+  BIND();
+  const FieldEntry& fe = field_entry(f);
+  const size_t aw = fe.abi_words, eb = aw * 4;
+  const pcdhip_buf *row[2][3], *col[2][3], *rcv[2][3], *val[2][3];  // [0]: on K, [1]: on B
+  for (int m = 0; m < 3; m++) for (int on_b = 0; on_b < 2; on_b++) {
+    const pcdhip_buf* v = index->vec[1 + on_b][m];
+    row[on_b][m] = &v[0]; col[on_b][m] = &v[1]; rcv[on_b][m] = &v[2]; val[on_b][m] = &v[3];
+  }
+  // one block: f on K and then its coefficients | the remainder | route 1: q on B -- route 2: a on B, b on B; both become coefficients,
+  // then a becomes q and b the product b f_poly, so each has room for the 4 |K| - 3 coefficients that a short B does not hold
+  const size_t slot_n = std::max(b_n, q_len), big = route == 1 ? slot_n : 2 * slot_n;
+  TRY(ctx->aux_ws.ensure(AUX_MARLIN_WS, (2 * k_n + big) * eb));
+  uint32_t* const fk = (uint32_t*)ctx->aux_ws.buf[AUX_MARLIN_WS];
+  uint32_t* const rem_ws = fk + k_n * aw;
+  uint32_t* const q = rem_ws + k_n * aw;
+  pcdhip_buf fbuf;
+  fbuf.field_id = f; fbuf.n = k_n; fbuf.dptr = f_poly ? f_poly->dptr : fk;
+  uint32_t* const rem = h2_rem ? h2_rem->dptr : rem_ws;
+  // f on K, interpolated; f_poly = sigma + X g_2
+  int rc = pcdhip_marlin_sumcheck_f(ctx, alpha_mont, beta_mont, coeff_mont, row[0], col[0], rcv[0], val[0], k_n, &fbuf);
+  rc = rc ? rc : transform_abi(ctx, f, dk, fbuf.dptr, k_n, fbuf.dptr, k_n, 1);
+  if (rc) return rc;
+  TRY(hipMemcpyAsync(sigma->dptr, fbuf.dptr, eb, hipMemcpyDeviceToDevice, ctx->stream));
+  if (g2_len) TRY(hipMemcpyAsync(g2->dptr, fbuf.dptr + aw, g2_len * eb, hipMemcpyDeviceToDevice, ctx->stream));
+  if (route == 1) {
+    // f on B, q = a - b f there in place, back to coefficients
+    rc = transform_abi(ctx, f, db, fbuf.dptr, k_n, q, b_n, 0);
+    if (rc) return rc;
+    const uint32_t* in[4][3];
+    for (int m = 0; m < 3; m++) { in[0][m] = row[1][m]->dptr; in[1][m] = col[1][m]->dptr; in[2][m] = rcv[1][m]->dptr; in[3][m] = val[1][m]->dptr; }
+    TRY(fe.marlin_sumcheck2_q(ctx->stream, (const uint32_t*)alpha_mont, (const uint32_t*)beta_mont, (const uint32_t*)coeff_mont, in[0], in[1], in[2],
+                              in[3], q, b_n, q));
+    rc = transform_abi(ctx, f, db, q, b_n, q, q_len, 1);
+    if (rc) return rc;
+  } else {
+    // upstream's order: a and b on B to coefficients (3 |K| - 2 each), b f_poly as a polynomial product over the domain of
+    // 4 |K| - 3 elements or more (pcdhip_poly_mul's steps, without its wait), a - b f_poly
+    uint32_t* const bq = q + slot_n * aw;
+    pcdhip_buf abuf, bbuf;
+    abuf.field_id = bbuf.field_id = f; abuf.n = bbuf.n = b_n; abuf.dptr = q; bbuf.dptr = bq;
+    rc = pcdhip_marlin_sumcheck_ab(ctx, alpha_mont, beta_mont, coeff_mont, row[1], col[1], rcv[1], val[1], b_n, &abuf, &bbuf);
+    rc = rc ? rc : transform_abi(ctx, f, db, q, b_n, q, b_n, 1);
+    rc = rc ? rc : transform_abi(ctx, f, db, bq, b_n, bq, b_n, 1);
+    if (rc) return rc;
+    const size_t ab_len = 3 * k_n - 2, vb = (size_t)dm.n * fe.words * 4;
+    TRY(ctx->aux_ws.ensure(AUX_FFT_X, vb));
+    TRY(ctx->aux_ws.ensure(AUX_FFT_TMP, vb));
+    TRY(ctx->aux_ws.ensure(AUX_MARLIN_MUL_B, vb));
+    uint32_t *x = (uint32_t*)ctx->aux_ws.buf[AUX_FFT_X], *y = (uint32_t*)ctx->aux_ws.buf[AUX_MARLIN_MUL_B], *tmp = (uint32_t*)ctx->aux_ws.buf[AUX_FFT_TMP];
+    const uint32_t* const src[2] = {bq, fbuf.dptr};
+    const size_t src_len[2] = {ab_len, k_n};
+    uint32_t* const dst[2] = {x, y};
+    for (int k = 0; k < 2; k++) {
+      TRY(fe.convert(ctx->stream, src[k], dst[k], (uint32_t)src_len[k], 0));
+      TRY(hipMemsetAsync(dst[k] + src_len[k] * fe.words, 0, (dm.n - src_len[k]) * fe.words * 4, ctx->stream));
+      rc = domain_transform(ctx, f, dm, dst[k], tmp, 0, 0, nullptr, nullptr);
+      if (rc) return rc;
+    }
+    TRY(fe.vec_mul(ctx->stream, x, y, dm.n, x, 0));
+    rc = domain_transform(ctx, f, dm, x, tmp, 1, 0, nullptr, nullptr);
+    if (rc) return rc;
+    TRY(fe.convert(ctx->stream, x, bq, (uint32_t)q_len, 1));
+    // a has 3 |K| - 2 coefficients, the product 4 |K| - 3: q = -(b f) beyond a's length
+    TRY(hipMemsetAsync(q + ab_len * aw, 0, (q_len - ab_len) * eb, ctx->stream));
+    TRY(fe.vec_addsub(ctx->stream, q, bq, q_len, 1, q));
+  }
+  // q = h_2 v_K + remainder
+  if (h2_len) TRY(fe.poly_div_vanishing(ctx->stream, q, q_len, k_n, h2->dptr, rem));
+  else TRY(hipMemcpyAsync(rem, q, eb, hipMemcpyDeviceToDevice, ctx->stream));  // (|K| = 1: q is one coefficient, all of it remainder)
+  out_lens[0] = g2_len; out_lens[1] = h2_len; out_lens[2] = (size_t)route;
   return PCDHIP_OK;
 }
 

@@ -340,6 +340,11 @@ struct FieldEntry {
   hipError_t (*vec_addsub)(hipStream_t, const uint32_t* a, const uint32_t* b, uint64_t n, int sub, uint32_t* out);
   // p += blind (X^n - 1), blind: k ABI coefficients on the device; p holds max(len, n + k) coefficients, those beyond len zeroed
   hipError_t (*poly_add_vanishing)(hipStream_t, uint32_t* p, const uint32_t* blind, uint64_t k, uint64_t n);
+  // K12 (marlin.hip.h marlin_sumcheck2_q): the second sumcheck's q_i = a_i - b_i f_i, a and b those of marlin_sumcheck_ab and never
+  // stored, one launch; q_out may be f
+  hipError_t (*marlin_sumcheck2_q)(hipStream_t, const uint32_t* alpha_abi, const uint32_t* beta_abi, const uint32_t* coeff_abi,
+                                   const uint32_t* const row[3], const uint32_t* const col[3], const uint32_t* const rc[3],
+                                   const uint32_t* const val[3], const uint32_t* f, uint64_t n, uint32_t* q_out);
 };
 const FieldEntry& field_entry(int field_id);
 

@@ -50,6 +50,10 @@ hipError_t PCD_CAT(pcd_marlin_sumcheck1_q_, PCD_FIELD_IDX)(hipStream_t, const ui
 hipError_t PCD_CAT(pcd_marlin_place_, PCD_FIELD_IDX)(hipStream_t, const uint32_t* z, uint64_t num_cols, uint64_t x_n, uint64_t h_n, uint32_t* out);
 hipError_t PCD_CAT(pcd_marlin_addsub_, PCD_FIELD_IDX)(hipStream_t, const uint32_t* a, const uint32_t* b, uint64_t n, int sub, uint32_t* out);
 hipError_t PCD_CAT(pcd_marlin_add_vanishing_, PCD_FIELD_IDX)(hipStream_t, uint32_t* p, const uint32_t* blind, uint64_t k, uint64_t n);
+// inst_marlin2.hip, K12: the second sumcheck's q = a - b f
+hipError_t PCD_CAT(pcd_marlin_sumcheck2_q_, PCD_FIELD_IDX)(hipStream_t, const uint32_t* alpha_abi, const uint32_t* beta_abi, const uint32_t* coeff_abi,
+                                                           const uint32_t* const row[3], const uint32_t* const col[3], const uint32_t* const rc[3],
+                                                           const uint32_t* const val[3], const uint32_t* f, uint64_t n, uint32_t* q_out);
 
 namespace {
 
@@ -650,7 +654,8 @@ const FieldEntry* PCD_CAT(pcd_field_entry_, PCD_FIELD_IDX)() {
                                poly_div_vanishing_run, poly_commit_scalars_run, marlin_lagrange_run, marlin_t_evals_run,
                                PCD_CAT(pcd_marlin_sumcheck_ab_, PCD_FIELD_IDX), PCD_CAT(pcd_marlin_index_arith_, PCD_FIELD_IDX),
                                PCD_CAT(pcd_marlin_sumcheck1_q_, PCD_FIELD_IDX), PCD_CAT(pcd_marlin_place_, PCD_FIELD_IDX),
-                               PCD_CAT(pcd_marlin_addsub_, PCD_FIELD_IDX), PCD_CAT(pcd_marlin_add_vanishing_, PCD_FIELD_IDX)};
+                               PCD_CAT(pcd_marlin_addsub_, PCD_FIELD_IDX), PCD_CAT(pcd_marlin_add_vanishing_, PCD_FIELD_IDX),
+                               PCD_CAT(pcd_marlin_sumcheck2_q_, PCD_FIELD_IDX)};
   return &e;
 }
 

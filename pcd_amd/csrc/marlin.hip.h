@@ -278,4 +278,51 @@ __global__ void __launch_bounds__(256) marlin_add_vanishing_multiple(uint32_t* p
   acc.canonical().pack32(p + idx * AW);
 }
 
+// ---- K12, the second sumcheck.
+// The pointwise core of its quotient: q_i = a_i - b_i f_i for i < n, a and b those of marlin_sumcheck_ab, from thirteen vectors read
+// once as ABI words and one store; a and b stay in registers.  The body up to the end of the loop is marlin_sumcheck_element's, line
+// for line, and on purpose a second copy of it: factored into a function that both kernels call (a and b handed back by reference,
+// or as a pair by value), the compiler's report for marlin_sumcheck_ab itself changed -- at 298 bits 108 -> 102 and 122 VGPRs, at 753
+// bits ScratchSize 0 -> 1300 bytes a lane and 2 -> 1 waves per SIMD -- so K9's kernel stays as it was and this one has its own text.
+// Scales: the loop leaves a and b on R, and f is read on R, so b f would land on R^2 / R' and no constant can mend that inside the
+// one product.  Instead f' = f cin is on R (R'^2 / R) / R' = R', then b f' is on R R' / R' = R beside a, and q = a - b f' is the ABI
+// image once canonical.  Two products beyond marlin_sumcheck_ab's: 19 with row_col, 17 without, at 16 product sites (its 14 and
+// these two).  The two are a chain -- no sum of two products stands in the formula -- so Fp::dot2 has nothing to fuse here:
+// dot2(a, R, -b, f) cin would be three products' multiply-adds under the same two reductions.  f is loaded behind the loop, so that
+// nothing of it is held across the loop's products; every load of element i still precedes the store and q_out is not declared
+// restrict, so q_out may be f.
+// element i of q (host and device, like marlin_sumcheck_element)
+template <class F>
+PCD_HD void marlin_sumcheck2_element(const MarlinSumcheckConsts<F>& k, const MarlinSumcheckIn& in, const uint32_t* f, uint64_t i,
+                                     uint32_t* q_out) {
+  constexpr int AW = F::ABI_WORDS;
+  const bool rc = in.rc[0] != nullptr;
+  F cin;
+#pragma unroll
+  for (int j = 0; j < F::N; j++) cin.v[j] = F::Params::cin(j);
+  const F row0 = F::unpack32(in.row[0] + i * AW), col0 = F::unpack32(in.col[0] + i * AW);
+  F b;
+  if (rc) b = k.ab_r - k.alpha_p * row0 - k.beta_p * col0 + F::unpack32(in.rc[0] + i * AW);
+  else b = ((k.beta_r - row0) * cin) * (k.alpha_r - col0);
+  F a = k.c[0] * F::unpack32(in.val[0] + i * AW);
+#pragma unroll 1
+  for (int m = 1; m < 3; m++) {
+    const F row = F::unpack32(in.row[m] + i * AW), col = F::unpack32(in.col[m] + i * AW);
+    F d;
+    if (rc) d = k.ab_p - k.alpha_2 * row - k.beta_2 * col + F::unpack32(in.rc[m] + i * AW) * cin;
+    else d = ((k.beta_r - row) * k.k3) * (k.alpha_r - col);
+    const F u = (m == 1 ? k.c[1] : k.c[2]) * F::unpack32(in.val[m] + i * AW);
+    a = a * d + u * b;
+    b = b * d;
+  }
+  const F fp = F::unpack32(f + i * AW) * cin;
+  (a - b * fp).canonical().pack32(q_out + i * AW);
+}
+template <class F>
+__global__ void __launch_bounds__(256) marlin_sumcheck2_q(const MarlinSumcheckConsts<F> k, const MarlinSumcheckIn in, const uint32_t* f,
+                                                          uint64_t n, uint32_t* q_out) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) marlin_sumcheck2_element<F>(k, in, f, i, q_out);
+}
+
 }  // namespace pcd

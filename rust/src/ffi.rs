@@ -138,6 +138,14 @@ extern "C" {
                                    z_poly: *const pcdhip_buf, len_z: usize, mask: *const pcdhip_buf, len_mask: usize, domain_d_n: usize,
                                    t_poly: *mut pcdhip_buf, h1: *mut pcdhip_buf, g1: *mut pcdhip_buf, sigma: *mut pcdhip_buf,
                                    out_lens: *mut usize) -> c_int;
+    // K12: Marlin's second sumcheck (q = a - b f in one launch; f, g_2 and h_2 from an index); row / col / row_col / val: arrays of
+    // three buffers each, row_col or its entries nullable; route: 0 auto, 1 pointwise on B, 2 by the polynomial product
+    pub fn pcdhip_marlin_sumcheck2_q(ctx: *mut pcdhip_ctx, alpha_mont: *const u64, beta_mont: *const u64, coeff_mont: *const u64,
+                                     row: *const *const pcdhip_buf, col: *const *const pcdhip_buf, row_col: *const *const pcdhip_buf,
+                                     val: *const *const pcdhip_buf, f: *const pcdhip_buf, n: usize, q_out: *mut pcdhip_buf) -> c_int;
+    pub fn pcdhip_marlin_sumcheck2(ctx: *mut pcdhip_ctx, index: *const pcdhip_marlin_index, alpha_mont: *const u64, beta_mont: *const u64,
+                                   coeff_mont: *const u64, route: c_int, f_poly: *mut pcdhip_buf, g2: *mut pcdhip_buf,
+                                   sigma: *mut pcdhip_buf, h2: *mut pcdhip_buf, h2_rem: *mut pcdhip_buf, out_lens: *mut usize) -> c_int;
 }
 
 /// `PCDHIP_E_*` (include/pcdhip.h)
