@@ -538,6 +538,63 @@ int pcdhip_kzg_commit(pcdhip_ctx* ctx, const pcdhip_bases* powers_of_g, const pc
  * (2, or 3 when an MSM's planes take several workgroups; 0 without a batch). */
 int pcdhip_kzg_commit_last_plan(pcdhip_ctx* ctx, uint64_t out[4]);
 
+/* ---- K13: a round's openings as one queued call ---------------------------------------------------------------------------
+ * The last prover step of a MarlinKZG10 proof, ark-poly-commit's `open_combinations` / `batch_open`, for polynomials that live on the
+ * device.  ark-poly-commit is not vendored here: the formula below is the contract, and what is said about upstream's order (its
+ * per-query accumulation over the labeled polynomials, the challenge xi_(j+1) on a degree-bound term) is restated from memory.
+ *
+ * Inputs: m items -- the records of pcdhip_kzg_commit: poly, len, blinding, shifted flag, shifted_offset, shifted_blinding -- and P
+ * openings.  Opening o has a point z_o (points_mont[o]) and two vectors of m ABI Montgomery elements, row o of coeffs_mont and of
+ * shifted_coeffs_mont (nullable: no degree-bound term anywhere):
+ *   a_(o,i)  the caller's collapse of its linear combinations and opening challenges onto the items; zero: item i is not in opening o;
+ *   s_(o,i)  non-zero only for items with `shifted`: the challenge that multiplies the item's degree-bound witness (upstream's xi_(j+1)).
+ * A constant term of a linear combination never changes a quotient ((c - c) / (X - z) = 0), so the interface has none: the caller adds
+ * it to the value.  For each opening
+ *   p_o = sum_i a_(o,i) p_i                          (its length the longest len_i with a_(o,i) != 0)
+ *   R_o = sum_i a_(o,i) blinding_i + sum_i s_(o,i) shifted_blinding_i
+ *   W_o = MSM(powers_of_g,                              (p_o - p_o(z_o)) / (X - z_o))
+ *       + sum_{i : s_(o,i) != 0} MSM(shifted_powers_of_g[shifted_offset_i ..], s_(o,i) (p_i - p_i(z_o)) / (X - z_o))
+ *       + MSM(powers_of_gamma_g,                        (R_o - R_o(z_o)) / (X - z_o))
+ *   value_o = p_o(z_o),   random_v_o = R_o(z_o).
+ * Both hiding parts are over the same bases, powers_of_gamma_g, so they are ONE polynomial R_o and ONE hiding MSM per opening: the same
+ * group element as upstream's two.  Lengths are taken as given (a device buffer is not trimmed): zeros at the top of len count.
+ *
+ * Every division of the call is a PART: the combined polynomial of each opening, R_o of each opening, and one single-term part per
+ * (o, i) with s_(o,i) != 0.  All parts run in three launches (combine + tile values, one carry scan, the tiles again from their carries,
+ * the canonical scalars scaled by s in the store); nothing waits for the host in between.
+ * Limits (PCDHIP_E_ARG beyond): m <= 1024, P <= 64, at most 8 non-zero s_(o,i) per opening, every len below 2^31. */
+/* The three launches alone, the testable core.  Tables of P x (2 + m) entries, entry [o][0] the combined polynomial, [o][1] R_o,
+ * [o][2 + i] the degree-bound term of item i: q_bufs (device buffers of field_id for the quotients' CANONICAL scalars, times s for a
+ * degree-bound term; an entry may be NULL when its part is absent or has a quotient of no coefficient, and q_bufs itself when all are),
+ * q_lens (out: the quotients' lengths, len - 1; 0 for an absent part) and values_mont (out: the part at z_o -- p_i(z_o), unscaled, for a
+ * degree-bound term; zero for an absent part).  A part is absent when no item with a buffer and len > 0 has a non-zero coefficient in
+ * it.  It waits once, to return the values.  PCDHIP_E_ARG: null required pointers, a buffer of another field or shorter than its
+ * length, s != 0 on an item without `shifted`, a quotient buffer that is missing, of another field or too short, the limits above;
+ * nothing is written then.  P == 0 succeeds without a launch. */
+int pcdhip_poly_open_quotients(pcdhip_ctx* ctx, int field_id, const pcdhip_kzg_commit_item* items, size_t m, size_t n_openings,
+                               const uint64_t* points_mont, const uint64_t* coeffs_mont, const uint64_t* shifted_coeffs_mont /* nullable */,
+                               pcdhip_buf* const* q_bufs, size_t* q_lens, uint64_t* values_mont);
+/* The whole round: the three launches, every opening's large MSMs (the combined quotient, and one per degree-bound term over
+ * shifted_powers_of_g from the item's shifted_offset) side by side on the streams of pcdhip_msm_submit, the hiding MSMs as ONE batched
+ * short chain under pcdhip_msm_set_short (one at a time otherwise), one epilogue that adds, normalises and copies back, ONE wait at the
+ * end.  Per opening: the affine W_o (x || y, ABI Montgomery) with its flag (the identity is flag 1 with zero coordinates), value_o and
+ * random_v_o (zero without a blinding).  An opening whose coefficients are all zero gives the identity and zero values.  P == 0
+ * succeeds without a launch.
+ * PCDHIP_E_ARG, with no output written: a combined quotient (len - 1 coefficients) longer than powers_of_g->n (upstream's
+ * TooManyCoefficients); shifted_offset + len - 1 above shifted_powers_of_g->n; R_o's quotient longer than powers_of_gamma_g->n;
+ * s != 0 on an item without `shifted`, or while shifted_powers_of_g is NULL; a blinding with a non-zero coefficient while
+ * powers_of_gamma_g is NULL; buffers that are not of the curve's scalar field; handles of different curves or not G1; sharded handles;
+ * outstanding MSM tickets (the rule of pcdhip_kzg_commit: the same side streams and workspaces); the limits above. */
+int pcdhip_kzg_batch_open(pcdhip_ctx* ctx, const pcdhip_bases* powers_of_g, const pcdhip_bases* powers_of_gamma_g /* nullable */,
+                          const pcdhip_bases* shifted_powers_of_g /* nullable */, const pcdhip_kzg_commit_item* items, size_t m,
+                          size_t n_openings, const uint64_t* points_mont, const uint64_t* coeffs_mont,
+                          const uint64_t* shifted_coeffs_mont /* nullable */, uint64_t* w_xy, uint8_t* w_inf, uint64_t* values_mont,
+                          uint64_t* random_v_mont);
+/* Which path the last pcdhip_kzg_batch_open of this context took: out[0] = large MSMs run, out[1] = hiding MSMs in the batched short
+ * chain, out[2] = hiding MSMs that ran one at a time, out[3] = launches of the division chain (3; 2 when every part is a constant; 0
+ * without a part). */
+int pcdhip_kzg_batch_open_last_plan(pcdhip_ctx* ctx, uint64_t out[4]);
+
 /* ---- K8 vector algebra for Marlin's AHP rounds ---------------------------------------------------------------------------
  * What the prover does with a polynomial between its transforms and its commitments, on device vectors of ABI Montgomery elements.
  * All buffers of one call are of the same field and a count may not exceed a buffer's n (PCDHIP_E_ARG otherwise, as for null

@@ -84,6 +84,7 @@ EXPORTS = [
     "pcdhip_marlin_mats_upload_ex", "pcdhip_marlin_zm_evals", "pcdhip_marlin_place_assignment", "pcdhip_poly_add_vanishing_multiple",
     "pcdhip_marlin_sumcheck1_q", "pcdhip_marlin_round1", "pcdhip_marlin_sumcheck1",
     "pcdhip_marlin_sumcheck2_q", "pcdhip_marlin_sumcheck2",
+    "pcdhip_poly_open_quotients", "pcdhip_kzg_batch_open", "pcdhip_kzg_batch_open_last_plan",
 ]
 
 
@@ -136,6 +137,9 @@ def lib():
         _LIB.pcdhip_marlin_sumcheck1.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, sz, vp, vp, vp, vp, szp]
         _LIB.pcdhip_marlin_sumcheck2_q.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
         _LIB.pcdhip_marlin_sumcheck2.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, szp]
+        _LIB.pcdhip_poly_open_quotients.argtypes = [vp, C.c_int, C.POINTER(KzgCommitItem), sz, sz, vp, vp, vp, vp, szp, vp]
+        _LIB.pcdhip_kzg_batch_open.argtypes = [vp, vp, vp, vp, C.POINTER(KzgCommitItem), sz, sz, vp, vp, vp, vp, vp, vp, vp]
+        _LIB.pcdhip_kzg_batch_open_last_plan.argtypes = [vp, vp]
     return _LIB
 
 
@@ -967,6 +971,84 @@ class Context:
         kzg_commit"""
         out = (C.c_uint64 * 4)()
         self._check(lib().pcdhip_kzg_commit_last_plan(self._ctx, out))
+        return tuple(int(v) for v in out)
+
+    # ---- K13: a round's openings as one call
+    @staticmethod
+    def _kzg_items(items):
+        """dicts as for kzg_commit -> the C array of pcdhip_kzg_commit_item"""
+        arr = (KzgCommitItem * max(len(items), 1))()
+        h = lambda b: b._h if b is not None else None
+        ln = lambda it, key, b: 0 if b is None else int(it.get(key, b.n) if it.get(key) is not None else b.n)
+        for a, it in zip(arr, items):
+            p, bl, sbl = it.get("poly"), it.get("blinding"), it.get("shifted_blinding")
+            a.poly, a.len = h(p), ln(it, "len", p)
+            a.blinding, a.blinding_len = h(bl), ln(it, "blinding_len", bl)
+            a.shifted_blinding, a.shifted_blinding_len = h(sbl), ln(it, "shifted_blinding_len", sbl)
+            a.shifted_offset, a.shifted = int(it.get("shifted_offset", 0)), 1 if it.get("shifted") else 0
+        return arr
+
+    @staticmethod
+    def _open_tables(field, m, points_mont, coeffs_mont, shifted_coeffs_mont):
+        L = FIELD_LIMBS[field]
+        pts = _u64(points_mont).reshape(-1, L)
+        P = pts.shape[0]
+        a = _u64(coeffs_mont).reshape(P, m, L) if m else np.zeros((P, 1, L), dtype=np.uint64)
+        s = None if shifted_coeffs_mont is None else (_u64(shifted_coeffs_mont).reshape(P, m, L) if m else np.zeros((P, 1, L), dtype=np.uint64))
+        return pts, P, a, s
+
+    def poly_open_quotients(self, field, items, points_mont, coeffs_mont, shifted_coeffs_mont=None, q_bufs=None):
+        """The three launches of a round's openings (pcdhip_poly_open_quotients).  `items` as for kzg_commit; points (P, L); coefficient
+        tables (P, m, L), ABI Montgomery.  -> (q_bufs, q_lens (P, 2 + m), values (P, 2 + m, L)): entry [o][0] the combined polynomial,
+        [o][1] the combined blinding polynomial, [o][2 + i] the degree-bound term of item i.  q_bufs: dict (o, k) -> DeviceBuf of canonical
+        scalars; allocated here from the items' lengths when not passed (the caller frees them)."""
+        m = len(items)
+        arr = self._kzg_items(items)
+        pts, P, a, s = self._open_tables(field, m, points_mont, coeffs_mont, shifted_coeffs_mont)
+        own = []
+        if q_bufs is None:
+            q_bufs = {}
+            for o in range(P):
+                nza = [bool(a[o, i].any()) for i in range(m)]
+                nzs = [s is not None and bool(s[o, i].any()) for i in range(m)]
+                lens = {0: max([arr[i].len for i in range(m) if nza[i]], default=0),
+                        1: max([arr[i].blinding_len for i in range(m) if nza[i] and arr[i].blinding] +
+                               [arr[i].shifted_blinding_len for i in range(m) if nzs[i] and arr[i].shifted_blinding], default=0)}
+                lens.update({2 + i: arr[i].len for i in range(m) if nzs[i]})
+                for k, n in lens.items():
+                    if n > 1:
+                        q_bufs[(o, k)] = self.buf_alloc(field, n - 1)
+                        own.append(q_bufs[(o, k)])
+        tab = (C.c_void_p * max(P * (2 + m), 1))()
+        for (o, k), b in q_bufs.items():
+            tab[o * (2 + m) + k] = b._h.value
+        q_lens = (C.c_size_t * max(P * (2 + m), 1))()
+        vals = np.zeros((P, 2 + m, FIELD_LIMBS[field]), dtype=np.uint64)
+        self._call_into(own, lambda: lib().pcdhip_poly_open_quotients(self._ctx, int(field), arr if m else None, m, P, _p(pts), _p(a), _p(s), tab, q_lens,
+                                                                      _p(vals)))
+        return q_bufs, np.array([int(x) for x in q_lens][:P * (2 + m)], dtype=np.uint64).reshape(P, 2 + m), vals
+
+    def kzg_batch_open(self, powers, items, points_mont, coeffs_mont, shifted_coeffs_mont=None, powers_of_gamma_g=None, shifted_powers=None):
+        """MarlinKZG10's open_combinations / batch_open over device-resident polynomials, one call that only queues
+        (pcdhip_kzg_batch_open) -> (w_xy (P, l1), w_inf (P,), values (P, L), random_v (P, L))"""
+        m = len(items)
+        field = CURVE_FR[powers.curve]
+        arr = self._kzg_items(items)
+        pts, P, a, s = self._open_tables(field, m, points_mont, coeffs_mont, shifted_coeffs_mont)
+        h = lambda b: b._h if b is not None else None
+        w = np.zeros((P, point_limbs(powers.curve, G1)), dtype=np.uint64)
+        winf = np.zeros(P, dtype=np.uint8)
+        v = np.zeros((P, FIELD_LIMBS[field]), dtype=np.uint64)
+        rv = np.zeros_like(v)
+        self._check(lib().pcdhip_kzg_batch_open(self._ctx, powers._h, h(powers_of_gamma_g), h(shifted_powers), arr if m else None, m, P, _p(pts),
+                                                _p(a), _p(s), _p(w), _p(winf), _p(v), _p(rv)))
+        return w, winf, v, rv
+
+    def kzg_batch_open_last_plan(self):
+        """(large MSMs run, hiding MSMs in the batched short chain, hiding MSMs one at a time, launches of the division chain) of the last
+        kzg_batch_open"""
+        out = (C.c_uint64 * 4)()
+        self._check(lib().pcdhip_kzg_batch_open_last_plan(self._ctx, out))
         return tuple(int(v) for v in out)
 
     def kzg_check(self, curve, g_xy, h_xy, beta_h_xy, comms_xy, points_mont, values_mont, w_xy, gamma_g_xy=None, random_v_mont=None,

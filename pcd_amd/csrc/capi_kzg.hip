@@ -8,7 +8,8 @@ using namespace pcd;
 
 namespace {
 // descriptors | values | tile scratch;  the two quotients of an opening;  everything of one pcdhip_kzg_commit call
-enum { AUX_POLY = AUX_FB_OUT + 1, AUX_POLY_Q, AUX_POLY_R, AUX_COMMIT };
+// (K13's calls take the slot of pcdhip_kzg_commit: neither runs while the other does, and a slot only ever grows)
+enum { AUX_POLY = AUX_FB_OUT + 1, AUX_POLY_Q, AUX_POLY_R, AUX_COMMIT, AUX_OPEN = AUX_COMMIT };
 
 // descriptors of k polynomials of one field (lens[j] <= their buffers' n, below 2^31) -> the field, or -1 when they do not qualify
 int poly_descs(const pcdhip_buf* const* polys, const size_t* lens, size_t k, std::vector<PolyDesc>* d, uint64_t* max_len) {
@@ -191,6 +192,235 @@ int kzg_commit_run(pcdhip_ctx* ctx, const pcdhip_bases* pg, const pcdhip_bases* 
   }
   return PCDHIP_OK;
 }
+
+// ---- K13: a round's openings.  What pcdhip_poly_open_quotients and pcdhip_kzg_batch_open have validated: the parts of the call
+// (common.h PolyOpenPart; src / work / q are filled in once the workspace is known), their terms, and where each part of opening o sits
+// in the P x (2 + m) table the C ABI speaks of -- [o][0] the combined polynomial, [o][1] R_o, [o][2 + i] the degree-bound term of item i.
+struct OpenPlan {
+  int field = -1;
+  size_t m = 0, P = 0;
+  std::vector<PolyOpenPart> parts;
+  std::vector<PolyOpenTerm> terms;
+  std::vector<int> part_of;        // P x (2 + m): the part's index, -1 when there is none
+  std::vector<size_t> slot_of;     // per part: its place in part_of
+  std::vector<size_t> work_off;    // per part: first element of its workspace vector ((size_t)-1: none)
+  std::vector<size_t> q_off;       // per part: first element of its quotient in one scalar area
+  size_t work_elems = 0, q_elems = 0;
+  uint64_t max_len = 0;
+  bool takes_blinding = false;     // some opening's R_o names a blinding buffer
+};
+constexpr size_t OPEN_MAX_ITEMS = 1024, OPEN_MAX_OPENINGS = 64, OPEN_MAX_DB = 8;
+
+bool abi_is_zero(const uint64_t* x, size_t limbs) { uint64_t o = 0; for (size_t i = 0; i < limbs; i++) o |= x[i]; return o == 0; }
+
+// -> PCDHIP_OK or PCDHIP_E_ARG; every buffer must be of `field`
+int open_plan(const pcdhip_kzg_commit_item* items, size_t m, size_t P, const uint64_t* coeffs, const uint64_t* scoeffs, int field, OpenPlan* pl) {
+  if (m > OPEN_MAX_ITEMS || P > OPEN_MAX_OPENINGS) return PCDHIP_E_ARG;
+  pl->m = m;
+  pl->P = P;
+  auto buf_ok = [&](const pcdhip_buf* b, uint64_t len) { return b->field_id == field && len <= b->n && len < (1ull << 31); };
+  for (size_t i = 0; i < m; i++) {
+    const pcdhip_kzg_commit_item& it = items[i];
+    if ((!it.poly && it.len) || (it.poly && !buf_ok(it.poly, it.len))) return PCDHIP_E_ARG;
+    if (it.blinding && !buf_ok(it.blinding, it.blinding_len)) return PCDHIP_E_ARG;
+    if (it.shifted_blinding && (!it.shifted || !buf_ok(it.shifted_blinding, it.shifted_blinding_len))) return PCDHIP_E_ARG;
+  }
+  pl->field = field;
+  pl->part_of.assign(P * (2 + m), -1);
+  const size_t L = (size_t)kFieldLimbs[field];
+  std::vector<uint64_t> one(L, 0);
+  with_host_field(field, [&](auto f) { decltype(f)::type::one().to_abi((uint32_t*)one.data()); });
+  auto coeff_idx = [&](const uint64_t* c, size_t idx) { return memcmp(c, one.data(), L * 8) == 0 ? POLY_OPEN_ONE : (uint32_t)idx; };
+  for (size_t o = 0; o < P; o++) {
+    bool first = true;
+    // a part from the terms [t0, end): dropped when it has none
+    auto close_part = [&](size_t t0, size_t slot, uint32_t scale) {
+      const size_t nt = pl->terms.size() - t0;
+      if (nt == 0) return;
+      PolyOpenPart pt = {};
+      for (size_t t = t0; t < pl->terms.size(); t++) pt.len = std::max<uint64_t>(pt.len, pl->terms[t].len);
+      pt.term_lo = (uint32_t)t0; pt.n_terms = (uint32_t)nt; pt.point = (uint32_t)o; pt.scale = scale;
+      pt.first_of_point = first ? 1 : 0;
+      first = false;
+      const bool own = nt == 1 && pl->terms[t0].coeff == POLY_OPEN_ONE;  // read from its item again: no workspace vector
+      pl->work_off.push_back(own ? (size_t)-1 : pl->work_elems);
+      if (!own) pl->work_elems += pt.len;
+      pl->q_off.push_back(pl->q_elems);
+      pl->q_elems += pt.len - 1;
+      pl->max_len = std::max(pl->max_len, pt.len);
+      pl->part_of[o * (2 + m) + slot] = (int)pl->parts.size();
+      pl->slot_of.push_back(o * (2 + m) + slot);
+      pl->parts.push_back(pt);
+    };
+    size_t t0 = pl->terms.size();
+    for (size_t i = 0; i < m; i++) {  // the combined polynomial
+      const uint64_t* a = coeffs + (o * m + i) * L;
+      if (!abi_is_zero(a, L) && items[i].len) pl->terms.push_back({items[i].poly->dptr, items[i].len, coeff_idx(a, o * m + i), 0});
+    }
+    close_part(t0, 0, POLY_OPEN_ONE);
+    t0 = pl->terms.size();
+    size_t db = 0;
+    for (size_t i = 0; i < m; i++) {  // R_o: both kinds of blinding over the same bases, one polynomial
+      const uint64_t* a = coeffs + (o * m + i) * L;
+      const uint64_t* s = scoeffs ? scoeffs + (o * m + i) * L : nullptr;
+      if (s && !abi_is_zero(s, L) && !items[i].shifted) return PCDHIP_E_ARG;
+      if (!abi_is_zero(a, L) && items[i].blinding) {
+        pl->takes_blinding = true;
+        if (items[i].blinding_len) pl->terms.push_back({items[i].blinding->dptr, items[i].blinding_len, coeff_idx(a, o * m + i), 0});
+      }
+      if (s && !abi_is_zero(s, L) && items[i].shifted_blinding) {
+        pl->takes_blinding = true;
+        if (items[i].shifted_blinding_len)
+          pl->terms.push_back({items[i].shifted_blinding->dptr, items[i].shifted_blinding_len, coeff_idx(s, (P + o) * m + i), 0});
+      }
+    }
+    close_part(t0, 1, POLY_OPEN_ONE);
+    for (size_t i = 0; scoeffs && i < m; i++) {  // the degree-bound terms: the item itself, its quotient scaled in the store
+      const uint64_t* s = scoeffs + (o * m + i) * L;
+      if (abi_is_zero(s, L)) continue;
+      if (++db > OPEN_MAX_DB) return PCDHIP_E_ARG;
+      if (!items[i].len) continue;
+      t0 = pl->terms.size();
+      pl->terms.push_back({items[i].poly->dptr, items[i].len, POLY_OPEN_ONE, 0});
+      close_part(t0, 2 + i, coeff_idx(s, (P + o) * m + i));
+    }
+  }
+  return PCDHIP_OK;
+}
+
+// The three launches of a plan on the context's stream.  The tables, the values and the scratch of the kernels sit at `base` (device,
+// open_tables_bytes(...) bytes); part y's workspace vector at work + work_off[y] elements; q[y] = where its quotient goes.  *values_dev:
+// one ABI element per part.  Asynchronous: the host vectors of `pl` are read by the staging copies, which return once they are staged.
+size_t open_tables_bytes(const OpenPlan& pl, const FieldEntry& fe, size_t off[6]) {
+  const size_t np = pl.parts.size(), eb = (size_t)fe.abi_words * 4;
+  off[0] = 0;                                                   // parts
+  off[1] = off[0] + up256(np * sizeof(PolyOpenPart));           // terms
+  off[2] = off[1] + up256(pl.terms.size() * sizeof(PolyOpenTerm));  // coefficients, then shifted coefficients
+  off[3] = off[2] + up256(2 * pl.P * pl.m * eb);                // points
+  off[4] = off[3] + up256(pl.P * eb);                           // values
+  off[5] = off[4] + up256(np * eb);                             // kernel scratch
+  return off[5] + up256(fe.poly_open_scratch_words((uint32_t)np, (uint32_t)pl.P, pl.max_len) * 4);
+}
+int open_run(pcdhip_ctx* ctx, OpenPlan& pl, char* base, uint32_t* work, uint32_t* const* q, const uint64_t* points, const uint64_t* coeffs,
+             const uint64_t* scoeffs, uint32_t** values_dev, uint32_t* launches) {
+  const FieldEntry& fe = field_entry(pl.field);
+  const size_t np = pl.parts.size(), eb = (size_t)fe.abi_words * 4, sw = (size_t)fe.abi_words;
+  size_t off[6];
+  open_tables_bytes(pl, fe, off);
+  for (size_t y = 0; y < np; y++) {
+    PolyOpenPart& pt = pl.parts[y];
+    pt.work = pl.work_off[y] == (size_t)-1 ? nullptr : work + pl.work_off[y] * sw;
+    pt.src = pt.work ? pt.work : pl.terms[pt.term_lo].p;
+    pt.q = q[y];
+  }
+  hipStream_t st = ctx->stream;
+  *values_dev = (uint32_t*)(base + off[4]);
+  if (np == 0) { if (launches) *launches = 0; return PCDHIP_OK; }  // (no coefficient anywhere: nothing to divide)
+  TRY(hipMemcpyAsync(base + off[0], pl.parts.data(), np * sizeof(PolyOpenPart), hipMemcpyHostToDevice, st));
+  TRY(hipMemcpyAsync(base + off[1], pl.terms.data(), pl.terms.size() * sizeof(PolyOpenTerm), hipMemcpyHostToDevice, st));
+  TRY(hipMemcpyAsync(base + off[2], coeffs, pl.P * pl.m * eb, hipMemcpyHostToDevice, st));
+  if (scoeffs) TRY(hipMemcpyAsync(base + off[2] + pl.P * pl.m * eb, scoeffs, pl.P * pl.m * eb, hipMemcpyHostToDevice, st));
+  TRY(hipMemcpyAsync(base + off[3], points, pl.P * eb, hipMemcpyHostToDevice, st));
+  TRY(fe.poly_open(st, (const PolyOpenPart*)(base + off[0]), (const PolyOpenTerm*)(base + off[1]), (const uint32_t*)(base + off[2]),
+                   (const uint32_t*)(base + off[3]), (uint32_t)np, (uint32_t)pl.P, pl.max_len, (uint32_t*)(base + off[5]), *values_dev, launches));
+  return PCDHIP_OK;
+}
+
+// Everything of pcdhip_kzg_batch_open behind its argument checks, in the shape of kzg_commit_run: the three launches of the divisions on
+// the context's stream, every opening's large MSMs (its combined quotient over powers_of_g, one per degree-bound term over
+// shifted_powers_of_g from the term's offset) on the side streams, slot = running index mod 4, the hiding MSMs batched or one at a time
+// on the context's stream, one epilogue over OPEN_SLOTS slots per opening, one copy back, ONE wait.
+constexpr size_t OPEN_SLOTS = 2 + OPEN_MAX_DB;  // combined, hiding, degree-bound terms; an absent part stays zero: Z = 0, the identity
+int kzg_batch_open_run(pcdhip_ctx* ctx, const pcdhip_bases* pg, const pcdhip_bases* pgg, const pcdhip_bases* sp, const pcdhip_kzg_commit_item* items,
+                       OpenPlan& pl, const uint64_t* points, const uint64_t* coeffs, const uint64_t* scoeffs, uint64_t* w_xy, uint8_t* w_inf,
+                       uint64_t* values_mont, uint64_t* random_v_mont) {
+  const GroupEntry& ge = group_entry(pg->curve_id, 1);
+  const FieldEntry& fe = field_entry(pl.field);
+  const size_t P = pl.P, m = pl.m, np = pl.parts.size(), sw = (size_t)fe.abi_words, eb = sw * 4;
+  const size_t jw = (size_t)ge.point_words / 2 * 3, jac_b = jw * 4, jac_abi_b = (size_t)ge.point_abi_words / 2 * 3 * 4, ab = (size_t)ge.point_abi_words * 4;
+  size_t off[6];
+  // tables and scratch | results, slot-major | their sums | the sums in the C-ABI image | what goes back: P affine points, then the
+  // parts' values | workspace vectors | quotient scalars
+  const size_t o_res = open_tables_bytes(pl, fe, off), o_sum = o_res + up256(OPEN_SLOTS * P * jac_b), o_abi = o_sum + up256(P * jac_b);
+  const size_t o_back = o_abi + up256(P * jac_abi_b), back_b = P * ab + np * eb, o_work = o_back + up256(back_b);
+  const size_t o_scal = o_work + up256(std::max<size_t>(pl.work_elems, 1) * eb);
+  TRY(ctx->aux_ws.ensure(AUX_OPEN, o_scal + std::max<size_t>(pl.q_elems, 1) * eb));
+  char* base = (char*)ctx->aux_ws.buf[AUX_OPEN];
+  uint32_t* res = (uint32_t*)(base + o_res);
+  uint32_t* scal = (uint32_t*)(base + o_scal);
+  std::vector<uint32_t*> q(np);
+  for (size_t y = 0; y < np; y++) q[y] = scal + pl.q_off[y] * sw;
+  hipStream_t st = ctx->stream;
+  TRY(hipMemsetAsync(res, 0, OPEN_SLOTS * P * jac_b, st));
+  uint32_t* values_dev = nullptr;
+  uint32_t launches = 0;
+  int rc = open_run(ctx, pl, base, (uint32_t*)(base + o_work), q.data(), points, coeffs, scoeffs, &values_dev, &launches);
+  if (rc) return rc;
+  TRY(hipEventRecord(ctx->g16_ready, st));
+  bool used[pcdhip_ctx::PIPE_SLOTS] = {};
+  uint64_t large = 0, running = 0, one_by_one = 0;
+  std::vector<MsmShortBatchIn> batch;
+  for (size_t o = 0; o < P; o++) {
+    size_t db_slot = 2;
+    for (size_t k = 0; k < 2 + m; k++) {
+      const int y = pl.part_of[o * (2 + m) + k];
+      if (y < 0) continue;
+      const uint64_t n = pl.parts[y].len - 1;
+      const size_t slot = (k < 2 ? k : db_slot++) * P + o;
+      if (n == 0) continue;  // (a constant: no quotient, the identity)
+      if (k == 1) {          // the hiding MSM, on the context's stream
+        if (n <= ctx->msm_short_max && batch.size() < HIDING_BATCH_MAX) { batch.push_back({q[y], 0u, (uint32_t)n, (uint32_t)slot}); continue; }
+        one_by_one++;
+        rc = commit_hiding_msm(ctx, pgg, q[y], (size_t)n, res + slot * jw);
+        if (rc) return rc;
+        continue;
+      }
+      const int s = (int)(running++ % pcdhip_ctx::PIPE_SLOTS);
+      MsmWorkspace& ws = ctx->g16_ws[2 + s];
+      hipStream_t sk = ctx->g16_streams[2 + s];
+      if (!used[s]) TRY(hipStreamWaitEvent(sk, ctx->g16_ready, 0));
+      used[s] = true;
+      TRY(ws.ensure(WS_OUT, jac_b + 64));
+      uint32_t* out_dev = (uint32_t*)ws.buf[WS_OUT];
+      const MsmBasesView bv = k == 0 ? pg->view(0) : sp->view((size_t)items[k - 2].shifted_offset);
+      ws.lane = ctx->g16_schedule == 2 && ctx->pipe_lane && ctx->lane.stream ? &ctx->lane : nullptr;
+      const hipError_t me = ge.msm(ws, sk, bv, q[y], (uint32_t)n, out_dev, ctx->msm_c, ctx->msm_chunk, ctx->msm_sort, nullptr, nullptr, MSM_SHARE_NONE);
+      ws.lane = nullptr;
+      TRY(me);
+      large++;
+      TRY(hipMemcpyAsync(res + slot * jw, out_dev, jac_b, hipMemcpyDeviceToDevice, sk));  // (before the workspace is used again)
+    }
+  }
+  for (int s = 0; s < pcdhip_ctx::PIPE_SLOTS; s++) if (used[s]) TRY(hipEventRecord(ctx->g16_end[2 + s], ctx->g16_streams[2 + s]));
+  uint32_t chain = 0;
+  if (!batch.empty()) {  // (the quotients are canonical by construction: no error word is read)
+    rc = msm_short_batch_async(ctx, pgg, batch.data(), batch.size(), res, jw, nullptr, &chain);
+    if (rc) return rc;
+  }
+  ctx->kzg_batch_open_plan[0] = large;
+  ctx->kzg_batch_open_plan[1] = batch.size();
+  ctx->kzg_batch_open_plan[2] = one_by_one;
+  ctx->kzg_batch_open_plan[3] = launches;
+  for (int s = 0; s < pcdhip_ctx::PIPE_SLOTS; s++) if (used[s]) TRY(hipStreamWaitEvent(st, ctx->g16_end[2 + s], 0));
+  TRY(ge.jac_sum_parts(st, res, P * jw, (uint32_t)OPEN_SLOTS, (uint32_t)P, (uint32_t*)(base + o_sum)));
+  TRY(ge.jac_out(st, (const uint32_t*)(base + o_sum), (uint32_t)P, (uint32_t*)(base + o_abi)));
+  TRY(ge.to_affine(st, (const uint32_t*)(base + o_abi), (uint32_t)P, (uint32_t*)(base + o_back)));
+  if (np) TRY(hipMemcpyAsync(base + o_back + P * ab, values_dev, np * eb, hipMemcpyDeviceToDevice, st));
+  std::vector<uint64_t> back((back_b + 7) / 8);
+  TRY(hipMemcpyAsync(back.data(), base + o_back, back_b, hipMemcpyDeviceToHost, st));
+  TRY(hipStreamSynchronize(st));
+  const size_t pl1 = ab / 8, L = sw / 2;
+  memcpy(w_xy, back.data(), P * ab);
+  memset(values_mont, 0, P * L * 8);
+  memset(random_v_mont, 0, P * L * 8);
+  for (size_t o = 0; o < P; o++) {
+    w_inf[o] = abi_is_zero(&back[o * pl1], pl1) ? 1 : 0;
+    const int yc = pl.part_of[o * (2 + m)], yr = pl.part_of[o * (2 + m) + 1];
+    if (yc >= 0) memcpy(values_mont + o * L, &back[P * pl1 + (size_t)yc * L], L * 8);
+    if (yr >= 0) memcpy(random_v_mont + o * L, &back[P * pl1 + (size_t)yr * L], L * 8);
+  }
+  return PCDHIP_OK;
+}
 void mont_to_canonical(int fr, const uint64_t* in, uint64_t* out) {
   with_host_field(fr, [&](auto f) { decltype(f)::type::from_abi((const uint32_t*)in).to_canonical_words((uint32_t*)out); });
 }
@@ -341,6 +571,98 @@ int pcdhip_kzg_commit(pcdhip_ctx* ctx, const pcdhip_bases* powers_of_g, const pc
 int pcdhip_kzg_commit_last_plan(pcdhip_ctx* ctx, uint64_t out[4]) {
   if (!ctx || !out) return PCDHIP_E_ARG;
   for (int i = 0; i < 4; i++) out[i] = ctx->kzg_commit_plan[i];
+  return PCDHIP_OK;
+}
+
+int pcdhip_poly_open_quotients(pcdhip_ctx* ctx, int field_id, const pcdhip_kzg_commit_item* items, size_t m, size_t n_openings, const uint64_t* points_mont,
+                               const uint64_t* coeffs_mont, const uint64_t* shifted_coeffs_mont, pcdhip_buf* const* q_bufs, size_t* q_lens,
+                               uint64_t* values_mont) {
+  return guarded([&]() -> int {
+  const size_t P = n_openings;
+  if (!ctx || !valid_field(field_id) || (m && !items) || (P && (!points_mont || !q_lens || !values_mont || (m && !coeffs_mont))))
+    return PCDHIP_E_ARG;
+  if (P == 0) return PCDHIP_OK;
+  OpenPlan pl;
+  int rc = open_plan(items, m, P, coeffs_mont, shifted_coeffs_mont, field_id, &pl);
+  if (rc) return rc;
+  const size_t np = pl.parts.size(), tab = P * (2 + m);
+  std::vector<uint32_t*> q(np, nullptr);
+  for (size_t y = 0; y < np; y++) {
+    if (pl.parts[y].len <= 1) continue;
+    const pcdhip_buf* b = q_bufs ? q_bufs[pl.slot_of[y]] : nullptr;
+    if (!b || b->field_id != pl.field || b->n < pl.parts[y].len - 1) return PCDHIP_E_ARG;
+    q[y] = b->dptr;
+  }
+  const size_t L = (size_t)kFieldLimbs[pl.field];
+  if (np == 0) {  // (no coefficient: every part is absent)
+    for (size_t s = 0; s < tab; s++) q_lens[s] = 0;
+    memset(values_mont, 0, tab * L * 8);
+    return PCDHIP_OK;
+  }
+  BIND();
+  const FieldEntry& fe = field_entry(pl.field);
+  const size_t eb = (size_t)fe.abi_words * 4;
+  size_t off[6];
+  const size_t o_work = open_tables_bytes(pl, fe, off);
+  TRY(ctx->aux_ws.ensure(AUX_OPEN, o_work + std::max<size_t>(pl.work_elems, 1) * eb));
+  char* base = (char*)ctx->aux_ws.buf[AUX_OPEN];
+  uint32_t* values_dev = nullptr;
+  rc = open_run(ctx, pl, base, (uint32_t*)(base + o_work), q.data(), points_mont, coeffs_mont, shifted_coeffs_mont, &values_dev, nullptr);
+  if (rc) return rc;
+  std::vector<uint64_t> vals(np * L);
+  TRY(hipMemcpyAsync(vals.data(), values_dev, np * eb, hipMemcpyDeviceToHost, ctx->stream));
+  TRY(hipStreamSynchronize(ctx->stream));
+  memset(values_mont, 0, tab * L * 8);
+  for (size_t s = 0; s < tab; s++) q_lens[s] = 0;
+  for (size_t y = 0; y < np; y++) {
+    q_lens[pl.slot_of[y]] = (size_t)(pl.parts[y].len - 1);
+    memcpy(values_mont + pl.slot_of[y] * L, &vals[y * L], L * 8);
+  }
+  return PCDHIP_OK;
+  });
+}
+
+int pcdhip_kzg_batch_open(pcdhip_ctx* ctx, const pcdhip_bases* powers_of_g, const pcdhip_bases* powers_of_gamma_g,
+                          const pcdhip_bases* shifted_powers_of_g, const pcdhip_kzg_commit_item* items, size_t m, size_t n_openings,
+                          const uint64_t* points_mont, const uint64_t* coeffs_mont, const uint64_t* shifted_coeffs_mont, uint64_t* w_xy,
+                          uint8_t* w_inf, uint64_t* values_mont, uint64_t* random_v_mont) {
+  return guarded([&]() -> int {
+  const size_t P = n_openings;
+  if (!ctx || !powers_of_g || (m && !items) || (P && (!points_mont || !w_xy || !w_inf || !values_mont || !random_v_mont || (m && !coeffs_mont))))
+    return PCDHIP_E_ARG;  // (before any handle is looked into)
+  const pcdhip_bases *pg = powers_of_g, *pgg = powers_of_gamma_g, *sp = shifted_powers_of_g;
+  auto g1_of_pg = [&](const pcdhip_bases* b) { return b->shards.empty() && b->group_id == 1 && b->curve_id == pg->curve_id; };
+  if (!valid_curve(pg->curve_id) || !g1_of_pg(pg) || (pgg && !g1_of_pg(pgg)) || (sp && !g1_of_pg(sp))) return PCDHIP_E_ARG;
+  if (pipe_pending(ctx)) return PCDHIP_E_ARG;  // submitted MSMs still own side-stream workspaces: collect them first
+  if (P == 0) return PCDHIP_OK;
+  const int fr = kCurveFr[pg->curve_id];
+  OpenPlan pl;
+  int rc = open_plan(items, m, P, coeffs_mont, shifted_coeffs_mont, fr, &pl);
+  if (rc) return rc;
+  if (pl.takes_blinding && !pgg) return PCDHIP_E_ARG;
+  for (size_t y = 0; y < pl.parts.size(); y++) {  // upstream's TooManyCoefficients, and the degree bound's room in the shifted powers
+    const size_t k = pl.slot_of[y] % (2 + m);
+    const uint64_t qn = pl.parts[y].len - 1;
+    if (k == 0 && qn > pg->n) return PCDHIP_E_ARG;
+    if (k == 1 && qn > pgg->n) return PCDHIP_E_ARG;
+    if (k >= 2 && (!sp || items[k - 2].shifted_offset > sp->n || qn > sp->n - items[k - 2].shifted_offset)) return PCDHIP_E_ARG;
+  }
+  if (shifted_coeffs_mont && !sp) {  // a degree-bound term of an empty item has no part, and still needs its handle
+    const size_t L = (size_t)kFieldLimbs[fr];
+    for (size_t s = 0; s < P * m; s++) if (!abi_is_zero(shifted_coeffs_mont + s * L, L)) return PCDHIP_E_ARG;
+  }
+  BIND();
+  rc = ensure_side_streams(ctx);
+  if (rc) return rc;
+  rc = kzg_batch_open_run(ctx, pg, pgg, sp, items, pl, points_mont, coeffs_mont, shifted_coeffs_mont, w_xy, w_inf, values_mont, random_v_mont);
+  if (rc) (void)hipDeviceSynchronize();  // (an error partway: nothing of this call stays in flight on the side streams, or reads the frames above)
+  return rc;
+  });
+}
+
+int pcdhip_kzg_batch_open_last_plan(pcdhip_ctx* ctx, uint64_t out[4]) {
+  if (!ctx || !out) return PCDHIP_E_ARG;
+  for (int i = 0; i < 4; i++) out[i] = ctx->kzg_batch_open_plan[i];
   return PCDHIP_OK;
 }
 

@@ -140,6 +140,8 @@ struct pcdhip_ctx {
   std::vector<uint32_t> short_batch_table;
   // pcdhip_kzg_commit_last_plan: large MSMs, hiding MSMs in the batch, hiding MSMs one at a time, launches of the batch chain
   uint64_t kzg_commit_plan[4] = {0, 0, 0, 0};
+  // pcdhip_kzg_batch_open_last_plan: large MSMs, hiding MSMs in the batch, hiding MSMs one at a time, launches of the division chain
+  uint64_t kzg_batch_open_plan[4] = {0, 0, 0, 0};
   // the MSMs of a Groth16 proof run concurrently, each on its own stream with its own workspace: the
   // latency-bound bucket-reduction tail of one overlaps the throughput-bound accumulation of the others.
   // Streams 0 and 1 are created with the highest priority, 2 with the default one, 3..5 with the lowest.
@@ -257,6 +259,22 @@ struct PolyDesc { const uint32_t* p; uint64_t len; };
 // one polynomial of the commit side (poly.hip.h poly_commit_scalars): a PolyDesc, the number of bases its MSM may use, and where its
 // canonical scalars go (min(len, cap) of them)
 struct PolyCommitDesc { const uint32_t* p; uint64_t len; uint64_t cap; uint32_t* out; };
+// K13 (poly.hip.h poly_open_*): one division of a batched opening call.  A part is the linear combination of its terms (the entries
+// [term_lo, term_lo + n_terms) of the call's term table), divided by (X - z) at the entry `point` of the call's table of points.
+// `coeff` / `scale` index the call's table of ABI Montgomery elements; POLY_OPEN_ONE stands for the constant 1 and reads nothing.
+// len = the longest term (at least 1: a part without coefficients is not in the table).  work: where the first launch stores the combined
+// coefficients (len ABI elements), null for a one-term part with coefficient 1; src: what the third launch divides, work or the item itself;
+// q: the part's len - 1 canonical scalars, each times `scale`.
+constexpr uint32_t POLY_OPEN_ONE = 0xffffffffu;
+struct PolyOpenTerm { const uint32_t* p; uint64_t len; uint32_t coeff, _pad; };
+struct PolyOpenPart {
+  uint64_t len;
+  const uint32_t* src;
+  uint32_t* work;
+  uint32_t* q;
+  uint32_t term_lo, n_terms, point, scale;
+  uint32_t first_of_point, _pad;  // != 0: this part's workgroup (0, y) leaves z^TILE of its point
+};
 struct FieldEntry {
   int words;      // u32 words per element, device-internal image
   int abi_words;  // u32 words per element at the C-ABI
@@ -345,6 +363,14 @@ struct FieldEntry {
   hipError_t (*marlin_sumcheck2_q)(hipStream_t, const uint32_t* alpha_abi, const uint32_t* beta_abi, const uint32_t* coeff_abi,
                                    const uint32_t* const row[3], const uint32_t* const col[3], const uint32_t* const rc[3],
                                    const uint32_t* const val[3], const uint32_t* f, uint64_t n, uint32_t* q_out);
+  // K13 (poly.hip.h poly_open_tiles / poly_open_carry_scan / poly_open_div_tiles): the n_parts divisions of parts_dev in three
+  // launches.  terms_dev, elts_abi_dev (coefficients and scales), points_abi_dev (n_points elements): the call's tables on the device;
+  // max_len = the longest part; scratch: poly_open_scratch_words(n_parts, n_points, max_len) u32 words; values_abi_dev[y] = part y at
+  // its point (ABI Montgomery).  *launches (nullable) = kernels launched
+  size_t (*poly_open_scratch_words)(uint32_t n_parts, uint32_t n_points, uint64_t max_len);
+  hipError_t (*poly_open)(hipStream_t, const PolyOpenPart* parts_dev, const PolyOpenTerm* terms_dev, const uint32_t* elts_abi_dev,
+                          const uint32_t* points_abi_dev, uint32_t n_parts, uint32_t n_points, uint64_t max_len, uint32_t* scratch,
+                          uint32_t* values_abi_dev, uint32_t* launches);
 };
 const FieldEntry& field_entry(int field_id);
 

@@ -54,6 +54,12 @@ hipError_t PCD_CAT(pcd_marlin_add_vanishing_, PCD_FIELD_IDX)(hipStream_t, uint32
 hipError_t PCD_CAT(pcd_marlin_sumcheck2_q_, PCD_FIELD_IDX)(hipStream_t, const uint32_t* alpha_abi, const uint32_t* beta_abi, const uint32_t* coeff_abi,
                                                            const uint32_t* const row[3], const uint32_t* const col[3], const uint32_t* const rc[3],
                                                            const uint32_t* const val[3], const uint32_t* f, uint64_t n, uint32_t* q_out);
+// inst_polyopen.hip, K13: the divisions of a round's openings, batched over parts
+size_t PCD_CAT(pcd_poly_open_scratch_words_, PCD_FIELD_IDX)(uint32_t n_parts, uint32_t n_points, uint64_t max_len);
+hipError_t PCD_CAT(pcd_poly_open_, PCD_FIELD_IDX)(hipStream_t, const PolyOpenPart* parts_dev, const PolyOpenTerm* terms_dev,
+                                                  const uint32_t* elts_abi_dev, const uint32_t* points_abi_dev, uint32_t n_parts,
+                                                  uint32_t n_points, uint64_t max_len, uint32_t* scratch, uint32_t* values_abi_dev,
+                                                  uint32_t* launches);
 
 namespace {
 
@@ -655,7 +661,8 @@ const FieldEntry* PCD_CAT(pcd_field_entry_, PCD_FIELD_IDX)() {
                                PCD_CAT(pcd_marlin_sumcheck_ab_, PCD_FIELD_IDX), PCD_CAT(pcd_marlin_index_arith_, PCD_FIELD_IDX),
                                PCD_CAT(pcd_marlin_sumcheck1_q_, PCD_FIELD_IDX), PCD_CAT(pcd_marlin_place_, PCD_FIELD_IDX),
                                PCD_CAT(pcd_marlin_addsub_, PCD_FIELD_IDX), PCD_CAT(pcd_marlin_add_vanishing_, PCD_FIELD_IDX),
-                               PCD_CAT(pcd_marlin_sumcheck2_q_, PCD_FIELD_IDX)};
+                               PCD_CAT(pcd_marlin_sumcheck2_q_, PCD_FIELD_IDX), PCD_CAT(pcd_poly_open_scratch_words_, PCD_FIELD_IDX),
+                               PCD_CAT(pcd_poly_open_, PCD_FIELD_IDX)};
   return &e;
 }
 

@@ -357,4 +357,162 @@ __global__ void __launch_bounds__(256) poly_div_vanishing(const uint32_t* __rest
   if (r && j < r_len) (acc + F::unpack32(p + j * AW)).canonical().pack32(r + j * AW);
 }
 
+// ---- K13, a round's openings (MarlinKZG10 `open_combinations` / `batch_open`): the three launches of the division above, batched over
+// PARTS (common.h PolyOpenPart), every part with its own terms, point, output slice and store scale.  grid (tiles of the longest part,
+// parts); a workgroup whose tile lies beyond its part's len leaves at once (whole workgroup).
+//
+// Launch 1 forms the part's tile in LDS as the linear combination of its terms and reduces it to T_k as poly_tile_eval does.  The B lanes
+// take the tile in E rounds of B consecutive elements: per round one accumulator per lane, and per term one contiguous run of B elements
+// staged through `sub` (which shares its storage with the reduction's `red`: the two are never live together).  The coefficients enter the
+// device image CS at a time through `cs`; a part of at most CS terms converts them once per workgroup.  The combined tile, reduced and
+// packed into `st`, is at once the Horner input and -- for a part with a workspace vector -- what is stored as ABI words for launch 3.
+template <class F>
+struct PolyOpenCfg {
+  static constexpr int CS = F::N <= 11 ? 32 : 8;  // (753 bits: st 48 KB + red 13.5 KB + cs 0.9 KB stays below 64 KB)
+};
+
+template <class F>
+__global__ void __launch_bounds__(PolyCfg<F>::B) poly_open_tiles(const PolyOpenPart* __restrict__ parts, const PolyOpenTerm* __restrict__ terms,
+                                                                 const uint32_t* __restrict__ elts_abi, const uint32_t* __restrict__ points_abi,
+                                                                 uint32_t* __restrict__ tiles, uint32_t tiles_stride, uint32_t* __restrict__ zt) {
+  constexpr int B = PolyCfg<F>::B, E = PolyCfg<F>::E, AW = F::ABI_WORDS, CS = PolyOpenCfg<F>::CS;
+  constexpr uint32_t TILE = PolyCfg<F>::TILE;
+  static_assert(F::WORDS >= AW, "sub fits into red");
+  __shared__ __attribute__((aligned(16))) uint32_t st[TILE * AW];
+  __shared__ __attribute__((aligned(16))) uint32_t red[B * F::WORDS];
+  __shared__ __attribute__((aligned(16))) uint32_t cs[CS * F::WORDS];
+  uint32_t* sub = red;
+  const PolyOpenPart d = parts[blockIdx.y];
+  const uint64_t lo = (uint64_t)blockIdx.x * TILE;
+  if (lo >= d.len) return;  // (whole workgroup; len >= 1, so tile 0 of every part runs)
+  const uint32_t cnt = (uint32_t)(d.len - lo < TILE ? d.len - lo : TILE);
+  const uint32_t t = threadIdx.x;
+  if (!d.work) {  // one term, coefficient 1: the item's own words
+    poly_stage_in<F, B>(terms[d.term_lo].p, lo, cnt, TILE, st);
+  } else {
+    const bool once = d.n_terms <= (uint32_t)CS;
+#pragma unroll 1
+    for (int e = 0; e < E; e++) {
+      const uint64_t elo = lo + (uint64_t)e * B;  // this round: elements [elo, elo + B)
+      F acc = F::zero();
+#pragma unroll 1
+      for (uint32_t j0 = 0; j0 < d.n_terms; j0 += CS) {
+        const uint32_t je = min(d.n_terms, j0 + CS);
+        if (!once || e == 0) {
+          __syncthreads();  // (the previous chunk's products have read cs)
+          if (j0 + t < je) {
+            const uint32_t c = terms[d.term_lo + j0 + t].coeff;
+            (c == POLY_OPEN_ONE ? F::one() : F::from_abi(elts_abi + (size_t)c * AW)).store(cs + (size_t)t * F::WORDS);
+          }
+        }
+#pragma unroll 1
+        for (uint32_t j = j0; j < je; j++) {
+          const PolyOpenTerm tm = terms[d.term_lo + j];
+          if (elo >= tm.len) continue;  // (uniform: the term ends below this round)
+          const uint32_t have = (uint32_t)(tm.len - elo < (uint64_t)B ? tm.len - elo : (uint64_t)B);
+          const uint32_t* src = tm.p + elo * AW;
+          __syncthreads();  // (cs is written; the previous term's products have read sub)
+          for (uint32_t w = t; w < (uint32_t)B * AW; w += B) sub[w] = w < have * AW ? src[w] : 0u;
+          __syncthreads();
+          acc = acc + F::load(cs + (size_t)(j - j0) * F::WORDS) * F::unpack32(sub + (size_t)t * AW);
+        }
+      }
+      acc.canonical().pack32(st + ((size_t)e * B + t) * AW);  // (zero at and beyond the part's len: no term reaches there)
+    }
+    __syncthreads();
+    uint32_t* dst = d.work + lo * AW;
+    for (uint32_t w = t; w < cnt * AW; w += B) dst[w] = st[w];
+  }
+  const F z = F::from_abi(points_abi + (size_t)d.point * AW);
+  F m = z;
+#pragma unroll
+  for (int e = 1; e < E; e++) m = m * z;  // z^E
+  __syncthreads();  // (st is whole; sub is no longer read, red may be written)
+  F h = poly_lane_horner<F, E>(st, F::zero(), true, z);
+  h = poly_block_reduce<F, B>(h, m, red);
+  if (t == 0) {
+    h.store(tiles + ((size_t)blockIdx.y * tiles_stride + blockIdx.x) * F::WORDS);
+    if (blockIdx.x == 0 && d.first_of_point) m.store(zt + (size_t)d.point * F::WORDS);  // m = (z^E)^B, once per POINT
+  }
+}
+
+// Launch 2: poly_carry_scan with the multiplier z^TILE read per part (a sibling, so that the kernel above keeps its code as it is).
+// values_abi[y] = part y at its point.
+template <class F>
+__global__ void __launch_bounds__(PolyCfg<F>::CB) poly_open_carry_scan(const PolyOpenPart* __restrict__ parts, const uint32_t* __restrict__ tiles,
+                                                                       uint32_t tiles_stride, const uint32_t* __restrict__ zt,
+                                                                       uint32_t* __restrict__ carries, uint32_t* __restrict__ values_abi) {
+  constexpr int CB = PolyCfg<F>::CB;
+  constexpr uint32_t TILE = PolyCfg<F>::TILE;
+  __shared__ __attribute__((aligned(16))) uint32_t red[CB * F::WORDS];
+  const PolyOpenPart d = parts[blockIdx.y];
+  const uint32_t K = (uint32_t)((d.len + TILE - 1) / TILE);
+  const uint32_t c = (K + CB - 1) / CB;
+  const uint32_t lo = min(K, threadIdx.x * c), hi = min(K, lo + c);
+  const uint32_t* T = tiles + (size_t)blockIdx.y * tiles_stride * F::WORDS;
+  const F Z = K > 1 ? F::load(zt + (size_t)d.point * F::WORDS) : F::one();
+  F h = F::zero();
+  for (uint32_t k = hi; k-- > lo;) h = F::load(T + (size_t)k * F::WORDS) + Z * h;
+  h = poly_block_suffix_scan<F, CB>(h, Z.pow_u64(c), red);
+  h.store(red + (size_t)threadIdx.x * F::WORDS);
+  __syncthreads();
+  F cin = threadIdx.x + 1 < (uint32_t)CB ? F::load(red + (size_t)(threadIdx.x + 1) * F::WORDS) : F::zero();
+  for (uint32_t k = hi; k-- > lo;) {
+    cin.store(carries + ((size_t)blockIdx.y * tiles_stride + k) * F::WORDS);
+    cin = F::load(T + (size_t)k * F::WORDS) + Z * cin;
+  }
+  if (threadIdx.x == 0) cin.canonical().pack32(values_abi + (size_t)blockIdx.y * F::ABI_WORDS);
+}
+
+// Launch 3: poly_div_tile<F, true> per part, from the part's own carries row, point and source.  The canonical store's constant is
+// kc * scale (kc = cin * 1 as there), formed by lane 0 and handed round through LDS: scaling the quotient by a challenge costs no product
+// beyond the one the canonical store pays anyway.
+template <class F>
+__global__ void __launch_bounds__(PolyCfg<F>::B) poly_open_div_tiles(const PolyOpenPart* __restrict__ parts, const uint32_t* __restrict__ elts_abi,
+                                                                     const uint32_t* __restrict__ points_abi, const uint32_t* __restrict__ carries,
+                                                                     uint32_t tiles_stride) {
+  constexpr int B = PolyCfg<F>::B, E = PolyCfg<F>::E, AW = F::ABI_WORDS;
+  constexpr uint32_t TILE = PolyCfg<F>::TILE;
+  __shared__ __attribute__((aligned(16))) uint32_t st[TILE * AW];
+  __shared__ __attribute__((aligned(16))) uint32_t red[B * F::WORDS];
+  __shared__ __attribute__((aligned(16))) uint32_t ks[F::WORDS];
+  const PolyOpenPart d = parts[blockIdx.y];
+  const uint64_t lo = (uint64_t)blockIdx.x * TILE;
+  if (lo >= d.len || d.len <= 1) return;  // (whole workgroup; a constant has no quotient)
+  const uint32_t cnt = (uint32_t)(d.len - lo < TILE ? d.len - lo : TILE);
+  poly_stage_in<F, B>(d.src, lo, cnt, TILE, st);
+  if (threadIdx.x == 0) {
+    F cin, one_raw = F::zero();
+#pragma unroll
+    for (int i = 0; i < F::N; i++) cin.v[i] = F::Params::cin(i);
+    one_raw.v[0] = 1;
+    F kc = cin * one_raw;
+    if (d.scale != POLY_OPEN_ONE) kc = kc * F::from_abi(elts_abi + (size_t)d.scale * AW);
+    kc.store(ks);
+  }
+  const F z = F::from_abi(points_abi + (size_t)d.point * AW);
+  F m = z;
+#pragma unroll
+  for (int e = 1; e < E; e++) m = m * z;
+  const F C = F::load(carries + ((size_t)blockIdx.y * tiles_stride + blockIdx.x) * F::WORDS);
+  const bool top = threadIdx.x == B - 1;
+  __syncthreads();
+  F h = poly_lane_horner<F, E>(st, top ? C : F::zero(), !top, z);
+  h = poly_block_suffix_scan<F, B>(h, m, red);
+  h.store(red + (size_t)threadIdx.x * F::WORDS);
+  __syncthreads();
+  F hin = top ? C : F::load(red + (size_t)(threadIdx.x + 1) * F::WORDS);
+  const F kc = F::load(ks);
+  const uint32_t base = threadIdx.x * E;
+#pragma unroll 1
+  for (int e = E - 1; e >= 0; e--) {
+    uint32_t* s = st + (size_t)(base + e) * AW;
+    hin = F::unpack32(s) + z * hin;
+    (hin * kc).canonical().pack32(s);
+  }
+  __syncthreads();
+  const uint32_t skip = lo == 0 ? AW : 0;
+  for (uint32_t w = threadIdx.x + skip; w < cnt * AW; w += B) d.q[lo * AW + w - AW] = st[w];
+}
+
 }  // namespace pcd
