@@ -300,7 +300,11 @@ int pcdhip_g16_pk_set_r1cs(pcdhip_ctx* ctx, pcdhip_g16_pk* pk, const pcdhip_csr*
  * the seven transforms + the pointwise step, both].  pcdhip_groth16_prove overlaps the same work with four of its MSMs. */
 int pcdhip_g16_witness_map_resident(pcdhip_ctx* ctx, const pcdhip_g16_pk* pk, const uint64_t* z_mont, uint64_t* h_out_mont,
                                     float out_ms[3]);
-/* proof_out = A (G1 x||y) || B (G2 x||y) || C (G1 x||y), affine Montgomery; inf_out[3]. */
+/* proof_out = A (G1 x||y) || B (G2 x||y) || C (G1 x||y), affine Montgomery; inf_out[3].  A point at infinity has flag 1 and zero
+ * coordinates; any of the three may be one (r = s = 0 is ark-groth16's create_proof_no_zk; A, B or C vanish for one value of r or s).
+ * r_mont and s_mont are ABI Montgomery elements of the scalar field and must be reduced: limbs that, read as an integer, are not below
+ * the modulus give PCDHIP_E_ARG before anything is queued (two elements compared on the host).  The entries of z_mont are NOT checked --
+ * that would be a host pass over num_vars elements on the hot path; the caller hands over reduced elements. */
 int pcdhip_groth16_prove(pcdhip_ctx* ctx, const pcdhip_g16_pk* pk, const pcdhip_csr* A, const pcdhip_csr* B,
                          const pcdhip_csr* C, const uint64_t* z_mont, const uint64_t* r_mont, const uint64_t* s_mont,
                          uint64_t* proof_out, uint8_t* inf_out);

@@ -458,6 +458,8 @@ int pcdhip_groth16_prove(pcdhip_ctx* ctx, const pcdhip_g16_pk* pk, const pcdhip_
                          const uint64_t* z, const uint64_t* r_mont, const uint64_t* s_mont, uint64_t* proof_out, uint8_t* inf_out) {
   return guarded([&]() -> int {
   if (!ctx || !pk || !z || !r_mont || !s_mont || !proof_out) return PCDHIP_E_ARG;
+  // (r + q would prove as r does -- Fp::from_abi reduces what it is given: a second encoding of the blinding factors is refused, not served)
+  if (!scalars_reduced(kCurveFr[pk->curve_id], r_mont, 1) || !scalars_reduced(kCurveFr[pk->curve_id], s_mont, 1)) return PCDHIP_E_ARG;
   if (A && B && C) { const pcdhip_csr* ms[3] = {A, B, C}; for (int k = 0; k < 3; k++) { int v = validate_csr(ms[k], pk->num_vars); if (v) return v; } }
   if (pipe_pending(ctx)) return PCDHIP_E_ARG;  // submitted MSMs still own side-stream workspaces: collect them first (before anything is queued)
   if (!pk->shards.empty()) return prove_sharded(ctx, pk, A, B, C, z, r_mont, s_mont, proof_out, inf_out);

@@ -118,6 +118,7 @@ int transpose_csr(const pcdhip_csr* m, size_t cols, size_t limbs, HostCsrT* t, c
 
 // ---- capi_verify.hip
 void negate_point(int curve_id, int group_id, uint64_t* xy);
+bool scalars_reduced(int fr, const uint64_t* x, size_t count);  // every element's limbs, as an integer, below the modulus of field `fr`
 void scalar_lincomb(int fr, const uint64_t* const* a, const uint64_t* const* b, size_t n, uint64_t* out);
 
 }  // namespace pcd

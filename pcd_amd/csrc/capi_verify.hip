@@ -39,10 +39,13 @@ int pairing_groups(pcdhip_ctx* ctx, int curve_id, const uint64_t* g1_xy, const u
   TRY(hipStreamSynchronize(ctx->stream));
   return PCDHIP_OK;
 }
+}  // namespace
 
+namespace pcd {
 // Are all `count` scalars (`into_repr()` images of field `fr`) reduced, i.e. < r?  On the host, before anything is enqueued: the window
 // tables read nwin * 8 bits of a scalar and drop the rest, the MSM refuses only what is wider than r, and either computes x + r as x --
 // so a public input >= r is a second encoding of another statement and is refused as an argument, not answered with a verdict.
+// (A limb compare with the modulus: it holds for the C-ABI Montgomery image as well, which pcdhip_groth16_prove checks r and s with.)
 bool scalars_reduced(int fr, const uint64_t* x, size_t count) {
   bool ok = true;
   with_host_field(fr, [&](auto f) {
@@ -61,7 +64,9 @@ bool scalars_reduced(int fr, const uint64_t* x, size_t count) {
   });
   return ok;
 }
+}  // namespace pcd
 
+namespace {
 // acc_i = gamma_abc[0] + sum_j x_ij gamma_abc[j] for k proofs (Jacobian C-ABI image -> affine + flags), through the resident bases
 // acc_z (nullable): when given, non-empty on return iff the accumulations came back in Jacobian form -- (X, Y) in acc_a, Z in acc_z -- which
 // happens with window tables and the wave-per-pairing kernels on (they take Jacobian G1 points: no inversion anywhere in a verification)
