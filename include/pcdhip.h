@@ -599,6 +599,75 @@ int pcdhip_kzg_batch_open(pcdhip_ctx* ctx, const pcdhip_bases* powers_of_g, cons
  * without a part). */
 int pcdhip_kzg_batch_open_last_plan(pcdhip_ctx* ctx, uint64_t out[4]);
 
+/* ---- K14: the MarlinKZG10 check, a round's openings verified in one call -------------------------------------------------
+ * The verifier's half of K13: ark-poly-commit's `MarlinKZG10::check_combinations` -> `batch_check`, the group and pairing work on the
+ * device (the verifier's scalar checks stay with the caller).  ark-poly-commit is not vendored here: the equation below is the
+ * contract.
+ *
+ * Inputs: m commitments comm_i; for the items with a degree bound a shifted commitment shifted_i and the index k(i) of the key's shift
+ * power S_k(i) = shifted_powers_of_g[shifted_offset_i] (upstream's `get_shift_power(bound)`), shift_index[i] = -1 for an item without a
+ * bound; and P openings.  Opening o has a point z_o, row o of the SAME two P x m tables that pcdhip_kzg_batch_open takes -- a_(o,i), and
+ * s_(o,i), non-zero only on degree-bound items: a prover's tables serve the verifier unchanged -- the claimed value_o and random_v_o, the
+ * claimed individual values v_(o,i) = p_i(z_o) wherever s_(o,i) != 0 (item_values_mont, P x m, read nowhere else), and the witness W_o.
+ *   C_o   = sum_i a_(o,i) comm_i + sum_i s_(o,i) (shifted_i - v_(o,i) S_k(i))
+ *   L_o   = C_o - value_o g - random_v_o gamma_g + z_o W_o
+ *   check : e(L_o, h) == e(W_o, beta_h)
+ * Equation e of E combines the openings with row e of an E x P matrix of randomizers rho: e(sum_o rho_o L_o, h) == e(sum_o rho_o W_o, beta_h).
+ * Each side is ONE MSM over the N = 2 + n_shift + 2 m + P points
+ *   [0] g   [1] gamma_g   [2 + k] S_k   [2 + n_shift + i] comm_i   [2 + n_shift + m + i] shifted_i   [2 + n_shift + 2 m + o] W_o
+ * with the left scalars
+ *   g: -sum_o rho_o value_o    gamma_g: -sum_o rho_o random_v_o    S_k: -sum_o sum_{i : k(i) = k} rho_o s_(o,i) v_(o,i)
+ *   comm_i: sum_o rho_o a_(o,i)    shifted_i: sum_o rho_o s_(o,i)    W_o: rho_o z_o
+ * and the right scalars rho_o over the W range.  Two modes:
+ *   combined     (randomizers_canonical given: P canonical scalars, the first one 1 as upstream draws them; the library draws none):
+ *                E = 1, one verdict in ok[0] -- upstream's batch_check;
+ *   per-opening  (randomizers_canonical == NULL): E = P, rho the identity matrix, ok[o] per opening, deterministic -- what finds the
+ *                culprit after a combined 0.
+ * Encodings are those of pcdhip_kzg_batch_open and pcdhip_kzg_check: affine points x || y in ABI Montgomery form with nullable flag
+ * bytes (a flagged point, and one with all-zero coordinates, is the identity), field elements in ABI Montgomery form, randomizers
+ * canonical.
+ *
+ * Refusals -- a bad encoding is an argument error, never a verdict; `ok` is left untouched on any error:
+ *   PCDHIP_E_SIZE_UNSUPPORTED  P > 64, or N > 1024 (the short MSM's limit);
+ *   PCDHIP_E_ARG, found on the host before anything is queued: null required pointers; any field input not reduced (>= r), Montgomery
+ *                tables and randomizers alike (item values where s != 0); s != 0 on an item whose shift_index is -1 or >= n_shift, or
+ *                while shift_index, shifted_xy or item_values_mont is NULL; random_v_mont given while the key has no gamma_g.
+ * A multi-device context addresses its device 0.  Everything runs on the context's own stream and its short-MSM workspace, which MSM
+ * tickets do not use. */
+typedef struct pcdhip_kzg_vk pcdhip_kzg_vk;
+/* The prepared verifier key: g, gamma_g (nullable: a key without hiding) and the n_shift shift powers resident in the device image in
+ * front of the range for a call's fresh points; h, beta_h and GT's one.  After it no call allocates or frees device memory, except to
+ * grow the key's scratch to the largest call seen (a Marlin-sized round fits from the start).  PCDHIP_E_SIZE_UNSUPPORTED for n_shift >
+ * 1022. */
+int pcdhip_kzg_vk_prepare(pcdhip_ctx* ctx, int curve_id, const uint64_t* g_xy, const uint64_t* gamma_g_xy /* nullable */, const uint64_t* h_xy,
+                          const uint64_t* beta_h_xy, const uint64_t* shift_powers_xy /* n_shift points; nullable with n_shift == 0 */,
+                          size_t n_shift, pcdhip_kzg_vk** out);
+void pcdhip_kzg_vk_free(pcdhip_ctx* ctx, pcdhip_kzg_vk* vk);
+/* The check.  One staged upload, one chain of launches (the fresh points into the device image, the scalar collapse, 2 E short MSMs
+ * over the key's vector as one batch, the hand-over of their Jacobian results to the pairing -- no inversion --, E two-pair pairings),
+ * one download, ONE wait.  ok: E verdicts (1 in combined mode, P per opening).  n_openings == 0 is true (ok[0] = 1) without a launch.
+ * Under pcdhip_pairing_set_mode(ctx, 1) the sums are normalised by one more launch; the verdicts are the same. */
+int pcdhip_kzg_check_combinations(pcdhip_ctx* ctx, pcdhip_kzg_vk* vk, size_t m, const uint64_t* comm_xy, const uint8_t* comm_inf /* nullable */,
+                                  const uint64_t* shifted_xy /* nullable */, const uint8_t* shifted_inf /* nullable */,
+                                  const int32_t* shift_index /* m entries, -1: no bound; nullable */, size_t n_openings,
+                                  const uint64_t* points_mont, const uint64_t* coeffs_mont, const uint64_t* shifted_coeffs_mont /* nullable */,
+                                  const uint64_t* values_mont, const uint64_t* random_v_mont /* nullable */,
+                                  const uint64_t* item_values_mont /* P x m, nullable; read only where s != 0 */, const uint64_t* w_xy,
+                                  const uint8_t* w_inf /* nullable */, const uint64_t* randomizers_canonical /* nullable: per-opening mode */,
+                                  int* ok);
+/* The scalar collapse alone, the testable core: the same tables of a field (no key: n_shift is an argument) -> the E x N left and the
+ * E x P right canonical scalars, in the order of the vector above.  It waits once, to return them.  The refusals of the check that need
+ * no points; n_openings == 0 succeeds without a launch. */
+int pcdhip_kzg_check_scalars(pcdhip_ctx* ctx, int field_id, size_t n_shift, size_t m, const int32_t* shift_index /* nullable */,
+                             size_t n_openings, const uint64_t* points_mont, const uint64_t* coeffs_mont,
+                             const uint64_t* shifted_coeffs_mont /* nullable */, const uint64_t* values_mont,
+                             const uint64_t* random_v_mont /* nullable */, const uint64_t* item_values_mont /* nullable */,
+                             const uint64_t* randomizers_canonical /* nullable */, uint64_t* left_canonical, uint64_t* right_canonical);
+/* What the last pcdhip_kzg_check_combinations of this context ran: out[0] = equations, out[1] = pairs of the left MSM (N), out[2] =
+ * kernel launches of the chain (7; 8 when the left MSM's planes take several workgroups, one more in pairing mode 1), out[3] = host
+ * waits (1). */
+int pcdhip_kzg_check_combinations_last_plan(pcdhip_ctx* ctx, uint64_t out[4]);
+
 /* ---- K8 vector algebra for Marlin's AHP rounds ---------------------------------------------------------------------------
  * What the prover does with a polynomial between its transforms and its commitments, on device vectors of ABI Montgomery elements.
  * All buffers of one call are of the same field and a count may not exceed a buffer's n (PCDHIP_E_ARG otherwise, as for null

@@ -85,6 +85,7 @@ EXPORTS = [
     "pcdhip_marlin_sumcheck1_q", "pcdhip_marlin_round1", "pcdhip_marlin_sumcheck1",
     "pcdhip_marlin_sumcheck2_q", "pcdhip_marlin_sumcheck2",
     "pcdhip_poly_open_quotients", "pcdhip_kzg_batch_open", "pcdhip_kzg_batch_open_last_plan",
+    "pcdhip_kzg_vk_prepare", "pcdhip_kzg_vk_free", "pcdhip_kzg_check_combinations", "pcdhip_kzg_check_scalars", "pcdhip_kzg_check_combinations_last_plan",
 ]
 
 
@@ -140,6 +141,12 @@ def lib():
         _LIB.pcdhip_poly_open_quotients.argtypes = [vp, C.c_int, C.POINTER(KzgCommitItem), sz, sz, vp, vp, vp, vp, szp, vp]
         _LIB.pcdhip_kzg_batch_open.argtypes = [vp, vp, vp, vp, C.POINTER(KzgCommitItem), sz, sz, vp, vp, vp, vp, vp, vp, vp]
         _LIB.pcdhip_kzg_batch_open_last_plan.argtypes = [vp, vp]
+        _LIB.pcdhip_kzg_vk_prepare.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, sz, vp]
+        _LIB.pcdhip_kzg_vk_free.argtypes = [vp, vp]
+        _LIB.pcdhip_kzg_vk_free.restype = None
+        _LIB.pcdhip_kzg_check_combinations.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, sz] + [vp] * 10
+        _LIB.pcdhip_kzg_check_scalars.argtypes = [vp, C.c_int, sz, sz, vp, sz] + [vp] * 9
+        _LIB.pcdhip_kzg_check_combinations_last_plan.argtypes = [vp, vp]
     return _LIB
 
 
@@ -1066,6 +1073,66 @@ class Context:
                                            _p(arr(random_v_mont, fl)), _p(arr(randomizers_canonical, fl)), C.byref(ok)))
         return ok.value == 1
 
+    # ---- K14: the MarlinKZG10 check
+    def kzg_vk_prepare(self, curve, g_xy, h_xy, beta_h_xy, gamma_g_xy=None, shift_powers_xy=None):
+        """The prepared verifier key of kzg_check_combinations (pcdhip_kzg_vk_prepare): g, gamma_g and the shift powers resident -> KzgVk"""
+        l1 = point_limbs(curve, G1)
+        sp = None if shift_powers_xy is None else _u64(shift_powers_xy).reshape(-1, l1)
+        h = C.c_void_p()
+        self._check(lib().pcdhip_kzg_vk_prepare(self._ctx, int(curve), _p(_u64(g_xy)), _p(None if gamma_g_xy is None else _u64(gamma_g_xy)),
+                                                _p(_u64(h_xy)), _p(_u64(beta_h_xy)), _p(sp), 0 if sp is None else sp.shape[0], C.byref(h)))
+        return KzgVk(self, h, curve, 0 if sp is None else sp.shape[0])
+
+    @staticmethod
+    def _check_tables(field, m, points_mont, coeffs_mont, shifted_coeffs_mont, values_mont, random_v_mont, item_values_mont, randomizers_canonical,
+                      shift_index):
+        L = FIELD_LIMBS[field]
+        pts, P, a, s = Context._open_tables(field, m, points_mont, coeffs_mont, shifted_coeffs_mont)
+        row = lambda x: None if x is None else _u64(x).reshape(P, L)
+        iv = None if item_values_mont is None else (_u64(item_values_mont).reshape(P, m, L) if m else np.zeros((P, 1, L), dtype=np.uint64))
+        idx = None if shift_index is None else np.ascontiguousarray(shift_index, dtype=np.int32).reshape(m)
+        return pts, P, a, s, row(values_mont), row(random_v_mont), iv, row(randomizers_canonical), idx
+
+    def kzg_check_scalars(self, field, n_shift, points_mont, coeffs_mont, values_mont, shifted_coeffs_mont=None, random_v_mont=None,
+                          item_values_mont=None, randomizers_canonical=None, shift_index=None):
+        """The scalar collapse of the check alone (pcdhip_kzg_check_scalars) -> (left (E, N, L), right (E, P, L)) canonical, N = 2 + n_shift +
+        2 m + P in the order g, gamma_g, shift powers, commitments, shifted commitments, witnesses; E = 1 with randomizers, P without"""
+        L = FIELD_LIMBS[field]
+        n_pts = np.size(points_mont) // L
+        m = np.size(coeffs_mont) // (n_pts * L) if n_pts else 0
+        pts, P, a, s, v, rv, iv, rnd, idx = self._check_tables(field, m, points_mont, coeffs_mont, shifted_coeffs_mont, values_mont, random_v_mont,
+                                                               item_values_mont, randomizers_canonical, shift_index)
+        E, N = (1 if rnd is not None else P), 2 + n_shift + 2 * m + P
+        left, right = np.zeros((E, N, L), dtype=np.uint64), np.zeros((E, P, L), dtype=np.uint64)
+        self._check(lib().pcdhip_kzg_check_scalars(self._ctx, int(field), n_shift, m, _p(idx), P, _p(pts), _p(a), _p(s), _p(v), _p(rv), _p(iv), _p(rnd),
+                                                   _p(left), _p(right)))
+        return left, right
+
+    def kzg_check_combinations(self, vk, comm_xy, points_mont, coeffs_mont, values_mont, w_xy, shifted_coeffs_mont=None, random_v_mont=None,
+                               item_values_mont=None, randomizers_canonical=None, shift_index=None, shifted_xy=None, comm_inf=None,
+                               shifted_inf=None, w_inf=None):
+        """MarlinKZG10's check_combinations / batch_check as one queued call (pcdhip_kzg_check_combinations).  The tables are those of
+        kzg_batch_open.  With randomizers (P canonical scalars, the first 1) -> one bool; without -> a list of P bools, one per opening."""
+        curve = vk.curve
+        field, l1 = CURVE_FR[curve], point_limbs(curve, G1)
+        cm = _u64(comm_xy).reshape(-1, l1)
+        m = cm.shape[0]
+        pts, P, a, s, v, rv, iv, rnd, idx = self._check_tables(field, m, points_mont, coeffs_mont, shifted_coeffs_mont, values_mont, random_v_mont,
+                                                               item_values_mont, randomizers_canonical, shift_index)
+        flags = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.uint8)
+        sh = None if shifted_xy is None else _u64(shifted_xy).reshape(m, l1)
+        ok = (C.c_int * max(P, 1))()
+        self._check(lib().pcdhip_kzg_check_combinations(self._ctx, vk._h, m, _p(cm) if m else None, _p(flags(comm_inf)), _p(sh), _p(flags(shifted_inf)),
+                                                        _p(idx), P, _p(pts), _p(a), _p(s), _p(v), _p(rv), _p(iv), _p(_u64(w_xy).reshape(P, l1)),
+                                                        _p(flags(w_inf)), _p(rnd), ok))
+        return ok[0] == 1 if (rnd is not None or P == 0) else [x == 1 for x in ok[:P]]
+
+    def kzg_check_combinations_last_plan(self):
+        """(equations run, pairs of the left MSM, kernel launches of the chain, host waits) of the last kzg_check_combinations"""
+        out = (C.c_uint64 * 4)()
+        self._check(lib().pcdhip_kzg_check_combinations_last_plan(self._ctx, out))
+        return tuple(int(v) for v in out)
+
     # ---- timing
     def timer_start(self):
         self._check(lib().pcdhip_timer_start(self._ctx))
@@ -1262,6 +1329,16 @@ class Pvk:
     def free(self):
         if self._h:
             lib().pcdhip_pvk_free(self.ctx._ctx, self._h)
+            self._h = None
+
+
+class KzgVk:
+    def __init__(self, ctx, h, curve, n_shift):
+        self.ctx, self._h, self.curve, self.n_shift = ctx, h, curve, n_shift
+
+    def free(self):
+        if self._h:
+            lib().pcdhip_kzg_vk_free(self.ctx._ctx, self._h)
             self._h = None
 
 

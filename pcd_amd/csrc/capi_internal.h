@@ -136,3 +136,24 @@ struct pcdhip_pvk {
   size_t abc_tables_off = 0;  // u32 words from abc_dev to the tables
 };
 constexpr size_t PVK_TABLE_INPUTS = 256;
+
+// the prepared verifier key of the MarlinKZG10 check (capi_kzg_check.hip), likewise unseen by the inst_*.hip units
+struct pcdhip_kzg_vk {
+  int curve_id = 0;
+  size_t n_shift = 0;
+  bool has_gamma = false;
+  // the check's vector in the device image, room for the short MSM's limit of points: g, gamma_g, the shift powers (resident), then a
+  // call's commitments, shifted commitments and witnesses.  `vec` is the handle the short MSM takes: its n and its infinity bitmap are
+  // set per call (the bitmap arrives with the call's upload); head_inf = the bits of the resident part
+  uint32_t* vec_dev = nullptr;
+  pcdhip_bases vec = {};
+  std::vector<uint32_t> head_inf;
+  // one block laid out once for the most equations a call may have: (h, beta_h) per equation, resident | the pairing's G1 slots | their
+  // Z | Miller values | GT results | Jacobian points in the C-ABI image (lane-per-pairing mode) -- byte offsets
+  void* pair = nullptr;
+  size_t o_g2 = 0, o_g1 = 0, o_z = 0, o_f = 0, o_gt = 0, o_jac = 0;
+  void* scratch = nullptr;  // a call's upload, its column scalars and MSM results; grows to the largest call seen
+  size_t scratch_bytes = 0;
+  std::vector<uint64_t> stage;   // the host image of the last call's upload (it outlives the staging copy)
+  std::vector<uint64_t> gt_one;
+};

@@ -142,6 +142,8 @@ struct pcdhip_ctx {
   uint64_t kzg_commit_plan[4] = {0, 0, 0, 0};
   // pcdhip_kzg_batch_open_last_plan: large MSMs, hiding MSMs in the batch, hiding MSMs one at a time, launches of the division chain
   uint64_t kzg_batch_open_plan[4] = {0, 0, 0, 0};
+  // pcdhip_kzg_check_combinations_last_plan: equations run, pairs of the left MSM, kernel launches of the chain, host waits
+  uint64_t kzg_check_plan[4] = {0, 0, 0, 0};
   // the MSMs of a Groth16 proof run concurrently, each on its own stream with its own workspace: the
   // latency-bound bucket-reduction tail of one overlaps the throughput-bound accumulation of the others.
   // Streams 0 and 1 are created with the highest priority, 2 with the default one, 3..5 with the lowest.
