@@ -367,6 +367,12 @@ int pcdhip_fixed_base_mul(pcdhip_ctx* ctx, int curve_id, int group_id, const uin
  * constraint synthesis, with the caller's randomness: toxic = [alpha, beta, gamma, delta, tau] (5 scalar-field
  * elements, Montgomery; tau must lie outside the evaluation domain, as upstream's
  * `sample_element_outside_domain` guarantees -- PCDHIP_E_ARG otherwise) and the two group generators.
+ * All five elements must be reduced and alpha, beta, gamma, delta non-zero (tau = 0 is legal), checked on the host
+ * before anything is queued -- PCDHIP_E_ARG otherwise: upstream unwraps the inverses of gamma and delta (a zero
+ * would panic there, and give a key of identities here), and the six single points alpha_g1 .. delta_g2 carry no
+ * infinity flag, so the identity cannot be returned in them.  A refused call leaves the context usable.
+ * num_constraints = 0 is accepted (n = 1, no h); l_query / l_inf may be NULL when num_inputs == num_vars, h_query /
+ * h_inf when n == 1.
  * QAP evaluation at tau (`instance_map_with_evaluation`: Lagrange coefficients, transposed mat-vecs) and every
  * fixed-base batch run on the device.  All output arrays are caller-allocated:
  * a / b_g1 / b_g2: num_vars points; gamma_abc_g1: num_inputs; l: num_vars - num_inputs;

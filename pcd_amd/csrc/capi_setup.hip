@@ -84,8 +84,15 @@ int pcdhip_groth16_setup(pcdhip_ctx* ctx, int curve_id, const pcdhip_csr* A, con
   if (!out->alpha_g1 || !out->beta_g1 || !out->delta_g1 || !out->beta_g2 || !out->gamma_g2 || !out->delta_g2 || !out->a_query ||
       !out->a_inf || !out->b_g1_query || !out->b_g1_inf || !out->b_g2_query || !out->b_g2_inf || !out->gamma_abc_g1 || !out->gamma_abc_inf)
     return PCDHIP_E_ARG;
-  BIND();
   const int fr = kCurveFr[curve_id];
+  // toxic waste, before anything is queued: all five reduced; alpha, beta, gamma, delta non-zero (upstream unwraps 1/gamma and 1/delta,
+  // and the six single points have no flag to say "identity").  The Montgomery image of zero is zero.
+  if (!scalars_reduced(fr, toxic, 5)) return PCDHIP_E_ARG;
+  for (size_t k = 0; k < 4; k++) {
+    const uint64_t* e = toxic + k * (size_t)kFieldLimbs[fr];
+    if (std::all_of(e, e + kFieldLimbs[fr], [](uint64_t w) { return w == 0; })) return PCDHIP_E_ARG;
+  }
+  BIND();
   const FieldEntry& fe = field_entry(fr);
   const size_t m = num_vars, ni = num_inputs, nc = A->num_rows, limbs = (size_t)kFieldLimbs[fr];
   if (m > ni && (!out->l_query || !out->l_inf)) return PCDHIP_E_ARG;
